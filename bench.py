@@ -14,7 +14,12 @@ single pass for N >= 2).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up steps, times K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`) and nothing more.
+  --dump-outputs DIR : after the timed steps rank 0 writes what the last timed step returned to DIR/<name>.npy
+                       (dump_outputs: every measurement, seeded samples of the parameters and Adam moments; < 64 MB).
+  --full             : everything below as well (each extra object can still be dropped with its --no-* switch).
+Extra objects (--full only):
   roofline     : the dominant kernel (the 256x256 k-major bf16 MFMA GEMM: forward + dX) timed
                  live with HIP events on the launch stream over the timed steps;
                  achieved = algorithmic FLOPs (2*M*N*K per launch) / event time.
@@ -30,6 +35,8 @@ Rank 0 prints ONE JSON line.  Extra objects:
                  config.tower_streams = 1, the A/B partner of the two-stream default), rank512_rccl.  Each entry:
                  value, unit, ms_per_step, steps, roofline_frac (the same GEMM family, live HIP
                  events), step_frac where the workload's matmul FLOPs are known, peak_hbm_gb.
+  bf16_stream  : (N = 1) the same step with config.residual_stream = "bfloat16", reported beside `value`.
+  rccl         : (N > 1, or BV_DP_FORCE_COLLECTIVES=1) evidence that the ranks joined one communicator.
 """
 import argparse
 import json
@@ -370,6 +377,51 @@ def rccl_info(comm, dev):
   return info
 
 
+DUMP_LEAF_SAMPLE = 16384        # elements kept per parameter leaf (leaves up to this size are written whole)
+DUMP_MOMENT_SAMPLE = 1 << 20    # elements kept of each flat optimizer moment buffer
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample_index(numel, k, seed):
+  """Sorted positions of a fixed, seeded sample of k out of numel elements (all of them when numel <= k)."""
+  import numpy as np
+  if numel <= k:
+    return np.arange(numel, dtype=np.int64)
+  return np.sort(np.random.default_rng(seed).choice(numel, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, state, meas):
+  """--dump-outputs: what one call of the timed update_fn hands its caller, as float32 / float64 .npy files.
+  Every measurement in full (0-d float64); the new parameters as `params.npy`, the concatenation over the sorted leaf
+  names of a sample of each leaf at positions seeded by the leaf's name (the same positions for any build with the same
+  parameter tree); the Adam moments as `opt_mu.npy` / `opt_nu.npy`, a seeded sample of the flat buffers."""
+  import zlib
+  import numpy as np
+  from big_vision_amd.params import flatten_tree
+  os.makedirs(out_dir, exist_ok=True)
+  arrays = {}
+  for k, v in sorted(meas.items()):
+    arrays[k] = np.asarray(float(torch.as_tensor(v).double().item()), dtype=np.float64)
+  parts = []
+  for name, v in sorted(flatten_tree(state["params"]).items()):
+    flat = v.detach().reshape(-1)
+    idx = _sample_index(flat.numel(), DUMP_LEAF_SAMPLE, zlib.crc32(name.encode()))
+    parts.append(flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+  arrays["params"] = np.concatenate(parts).astype(np.float32)
+  opt = state["opt"]
+  for key in ("mu", "nu"):
+    buf = getattr(opt, key, None)
+    if isinstance(buf, torch.Tensor) and buf.numel():
+      idx = _sample_index(buf.numel(), DUMP_MOMENT_SAMPLE, zlib.crc32(b"opt"))   # the same positions in mu and nu
+      arrays[f"opt_{key}"] = buf[torch.from_numpy(idx).to(buf.device)].float().cpu().numpy().astype(np.float32)
+  total = sum(a.nbytes for a in arrays.values())
+  if total > DUMP_MAX_BYTES:
+    raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+  for k, a in arrays.items():
+    np.save(os.path.join(out_dir, f"{k}.npy"), a)
+  return sorted(arrays)
+
+
 def _free_port():
   import socket
   with socket.socket() as sk:
@@ -607,7 +659,7 @@ def configs_object(dev, steps=3):
   return out
 
 
-def main():
+def parse_args(argv=None):
   ap = argparse.ArgumentParser()
   ap.add_argument("--gpus", type=int, default=1)
   ap.add_argument("--steps", type=int, default=4)
@@ -626,7 +678,21 @@ def main():
   ap.add_argument("--microbatch", type=int, default=MICRO, help="pairs per micro-batch and rank")
   ap.add_argument("--residual-stream", default=RESIDUAL_STREAM, choices=("float32", "bfloat16"),
                   help="dtype of the activations between the encoder blocks (config.residual_stream)")
-  args = ap.parse_args()
+  ap.add_argument("--full", action="store_true",
+                  help="also measure and check everything beyond the headline: roofline (per-launch HIP events, one-stream "
+                       "step, rocprofv3 --pmc child passes), bf16_stream, configs, cpu_baseline and rccl (the --no-* "
+                       "switches still drop single parts); without it the run times the headline alone")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write what the last timed step returned (measurements, a seeded sample "
+                       "of the parameters and optimizer moments) as DIR/<name>.npy")
+  args = ap.parse_args(argv)
+  if not args.full:
+    args.no_roofline = args.no_cpu_baseline = args.no_bf16_stream = args.no_configs = args.no_live_pmc = True
+  return args
+
+
+def main():
+  args = parse_args()
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     return spawn_ranks(args.gpus)   # plain `python bench.py --gpus N`: one process per GPU, started here
@@ -664,9 +730,10 @@ def main():
   image, text = synthetic_batch(n, dev, seed=1 + comm.rank)
   batch = {"image": image, "labels": text}
 
-  def measure(stream, steps, warmup, roofline):
+  def measure(stream, steps, warmup, roofline, dump_dir=None):
     """W untimed + K timed steps of the full training step on `stream`; everything it allocates is freed
-    on return (the second, bf16-stream measurement at N = 1 needs the HBM back)."""
+    on return (the second, bf16-stream measurement at N = 1 needs the HBM back).  dump_dir: rank 0 writes what
+    the last timed step returned there (dump_outputs), before anything else touches the state."""
     model = two_towers.Model(image=IMAGE_CFG, text=TEXT_CFG, out_dim=(None, EMB),   # (the model caches its
                              temperature_init=10.0, bias_init=-10.0)                # executors: one per measurement)
     config = make_config(total_steps)
@@ -710,6 +777,8 @@ def main():
     dt = float(t.item())
     loss = float(meas["training_loss"].item())
     siglip.check_finite(meas)
+    if dump_dir is not None and comm.rank == 0:
+      dump_outputs(dump_dir, state, meas)
     # One EXTRA, untimed step with both towers on one stream and the same per-launch events: launches are serialised,
     # so the family's busy time there is exclusive by construction.  Reported as `roofline.one_stream` beside the
     # timed region's figure (on two streams a family launch that runs beside the other tower's LayerNorm / attention
@@ -742,7 +811,7 @@ def main():
     del state, update_fn, meas, model
     return res
 
-  r = measure(args.residual_stream, args.steps, args.warmup, not args.no_roofline)
+  r = measure(args.residual_stream, args.steps, args.warmup, not args.no_roofline, dump_dir=args.dump_outputs)
   dt, host_dt, host_unblocked_ms, loss, obs = r["dt"], r["host_dt"], r["host_unblocked_ms"], r["loss"], r["obs"]
   # N = 1 only: the opt-in bf16 residual stream on the same workload, as a separate object of the line
   bf16_line = None
@@ -764,7 +833,7 @@ def main():
       bf16_line = {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
 
   # (a collective: every rank takes part, then the others are done)
-  rccl = rccl_info(comm, dev) if (world > 1 or os.environ.get("BV_DP_FORCE_COLLECTIVES") == "1") else None
+  rccl = rccl_info(comm, dev) if args.full and (world > 1 or os.environ.get("BV_DP_FORCE_COLLECTIVES") == "1") else None
   if comm.rank != 0:
     return
   roof = None

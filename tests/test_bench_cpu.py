@@ -85,3 +85,48 @@ def test_pmc_family_totals_reads_a_counter_file(tmp_path):
       f.write(f'{i},{i},0,1,1,1,131072,{i},"{name}",512,163840,0,240,0,96,"FETCH_SIZE",{val},{1000 * i},{1000 * i + 500}\n')
   kib, n = bench.pmc_family_totals(str(p))
   assert n == 3 and kib == 1750.0
+
+
+def test_plain_run_times_the_headline_alone_and_full_keeps_every_extra():
+  """A plain `bench.py --steps K --warmup W` switches every extra measurement off; --full runs them as before, and its
+  --no-* switches still drop single objects."""
+  plain = bench.parse_args(["--steps", "3", "--warmup", "2"])
+  assert plain.steps == 3 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+  assert plain.no_roofline and plain.no_cpu_baseline and plain.no_bf16_stream and plain.no_configs and plain.no_live_pmc
+  full = bench.parse_args(["--full"])
+  assert full.full and not (full.no_roofline or full.no_cpu_baseline or full.no_bf16_stream or full.no_configs
+                            or full.no_live_pmc)
+  part = bench.parse_args(["--full", "--no-configs"])
+  assert part.no_configs and not part.no_roofline and not part.no_cpu_baseline
+  assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_dump_outputs_writes_seeded_float_samples(tmp_path):
+  """dump_outputs: every measurement as a 0-d float64 array, seeded per-leaf samples of the parameters and samples of
+  the Adam moments as float32 - the same positions on every call, within the 64 MB budget."""
+  import numpy as np
+  import torch
+
+  class Opt:
+    mu = torch.arange(3 << 20, dtype=torch.float32)
+    nu = torch.arange(3 << 20, dtype=torch.float32) * 2
+  big = torch.arange(100_000, dtype=torch.float32).reshape(100, 1000)
+  small = torch.arange(10, dtype=torch.float32)
+  state = {"params": {"img": {"w": big}, "t": small}, "opt": Opt()}
+  meas = {"training_loss": torch.tensor(1.5), "l2_grads": torch.tensor(0.25, dtype=torch.float64)}
+  names = bench.dump_outputs(str(tmp_path / "a"), state, meas)
+  assert names == ["l2_grads", "opt_mu", "opt_nu", "params", "training_loss"]
+  a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+  assert a["training_loss"].dtype == np.float64 and a["training_loss"].shape == () and a["training_loss"] == 1.5
+  assert a["l2_grads"] == 0.25
+  p = a["params"]
+  assert p.dtype == np.float32 and p.shape == (bench.DUMP_LEAF_SAMPLE + 10,)
+  head = p[:bench.DUMP_LEAF_SAMPLE]               # "img/w" sorts before "t"
+  assert np.all(np.diff(head) > 0) and head.max() < 100_000 and np.array_equal(head, np.round(head))
+  assert np.array_equal(p[bench.DUMP_LEAF_SAMPLE:], np.arange(10, dtype=np.float32))   # small leaves whole
+  assert a["opt_mu"].shape == (bench.DUMP_MOMENT_SAMPLE,) and a["opt_mu"].dtype == np.float32
+  assert np.array_equal(a["opt_nu"], 2 * a["opt_mu"]) and np.all(np.diff(a["opt_mu"]) > 0)   # same sorted positions
+  bench.dump_outputs(str(tmp_path / "b"), state, meas)
+  for n in names:
+    assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+  assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES

@@ -180,8 +180,8 @@ def test_bench_line_of_two_ranks_sharing_one_gpu():
   env = dict(os.environ, BV_BENCH_SHARE_GPU="1", BV_DP_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
   for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k, None)
-  r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--global-batch", "64", "--steps", "2",
-                      "--warmup", "1", "--cpu-sample", "2"], env=env, capture_output=True, text=True, timeout=900)
+  r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--global-batch", "64", "--steps",
+                      "2", "--warmup", "1", "--cpu-sample", "2"], env=env, capture_output=True, text=True, timeout=900)
   assert r.returncode == 0, r.stderr[-2000:]
   lines = [l for l in r.stdout.splitlines() if l.strip()]
   assert len(lines) == 1, r.stdout[-1000:]
@@ -191,6 +191,28 @@ def test_bench_line_of_two_ranks_sharing_one_gpu():
   assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
   assert d["roofline"]["bound"] == "mfma" and d["roofline"]["launches"] > 0 and "measured_on" in d["roofline"]
   assert "shared_gpu" in d["config"] and d["value"] > 0 and math.isfinite(d["config"]["final_loss"])
+
+
+def test_plain_bench_line_of_two_ranks_sharing_one_gpu(tmp_path):
+  """The plain N > 1 run (no --full): both ranks time the sharded-loss step, the non-zero rank leaves right after its
+  timed region, rank 0 prints ONE headline line without the --full objects and alone writes --dump-outputs."""
+  import json
+  import subprocess
+  env = dict(os.environ, BV_BENCH_SHARE_GPU="1", BV_DP_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+  for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+    env.pop(k, None)
+  out = tmp_path / "dump"
+  r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--global-batch", "64", "--steps", "2",
+                      "--warmup", "1", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900)
+  assert r.returncode == 0, r.stderr[-2000:]
+  lines = [l for l in r.stdout.splitlines() if l.strip()]
+  assert len(lines) == 1, r.stdout[-1000:]
+  d = json.loads(lines[0])
+  assert d["n_gpus"] == 2 and d["steps"] == 2 and d["config"]["per_gpu_batch"] == 32 and d["config"]["parallelism"] == "dp2"
+  assert d["value"] > 0 and d["ms_per_step"] > 0 and math.isfinite(d["config"]["final_loss"]) and "shared_gpu" in d["config"]
+  for key in ("roofline", "cpu_baseline", "rccl", "bf16_stream", "configs"):
+    assert key not in d, key
+  assert {"training_loss.npy", "params.npy", "opt_mu.npy", "opt_nu.npy"} <= set(os.listdir(out))
 
 
 def test_bench_line_under_torchrun_sharing_one_gpu():
@@ -207,8 +229,8 @@ def test_bench_line_under_torchrun_sharing_one_gpu():
   for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k, None)
   r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                      "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--global-batch",
-                      "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "2"], env=env, capture_output=True, text=True,
+                      "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+                      "--global-batch", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "2"], env=env, capture_output=True, text=True,
                      timeout=900)
   assert r.returncode == 0, r.stderr[-2000:]
   lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -1,5 +1,5 @@
 """Bench lines for the BASELINE.json configs other than the headline one (bench.py = configs[2]); the workloads
-themselves live in bench.py (its N = 1 line carries them as the `configs` object), this is the stand-alone CLI:
+themselves live in bench.py (its N = 1 `--full` line carries them as the `configs` object), this is the stand-alone CLI:
 
   c2  ViT-B/16 image tower alone, forward + backward, batch 256                     (configs[1])
   c4  SigLIP ViT-L/16 @336 px + text-L, global batch 8192 on 8 GPUs = 1024 pairs per GPU: one

@@ -23,12 +23,12 @@ if [[ " $* " == *" gemm_order "* ]]; then
   python tools/gemm_group_pmc.py parse $(find $O/pmc -name "*counter_collection.csv" | head -1) 2>&1 | tee $O/group_pmc.txt
   rm -rf $O/pmc
   for g in 4 0 4 0; do
-    timeout 300 python tools/gemm_group_ab.py --step $g --steps 3 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs > $O/step_g$g.json 2> /dev/null
+    timeout 300 python tools/gemm_group_ab.py --step $g --full --steps 3 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs > $O/step_g$g.json 2> /dev/null
     echo "group_n=$g $(python -c "import json; d=json.load(open('$O/step_g$g.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'])")" | tee -a $O/group_step.txt
   done
 fi
 if [[ " $* " == *" quick "* ]]; then
-  timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs > $O/headline.json 2> $O/headline.err
+  timeout 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs > $O/headline.json 2> $O/headline.err
   python -c "import json; d=json.load(open('$O/headline.json')); print('headline', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('step_frac'))"
   timeout 300 python bench.py --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream --no-configs --no-roofline > $O/n512.json 2> $O/n512.err
   python -c "import json; d=json.load(open('$O/n512.json')); print('n512', d['value'], d['ms_per_step'])"

@@ -16,12 +16,12 @@ if [[ " $* " == *" tests "* ]]; then
   cp gpurun_out/parity_report.jsonl $O/parity_report.jsonl 2>/dev/null
 fi
 if [[ " $* " == *" bench "* ]]; then
-  timeout 900 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-600 $O/bench_line.json
-  RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 BV_DP_FORCE_COLLECTIVES=1 timeout 300 python bench.py --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-bf16-stream > $O/bench_n512_rccl.json 2> $O/bench_n512_rccl.err; tail -2 $O/bench_n512_rccl.err; cut -c1-300 $O/bench_n512_rccl.json
-  timeout 300 python bench.py --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream > $O/bench_n512.json 2> $O/bench_n512.err; cut -c1-300 $O/bench_n512.json
+  timeout 900 python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-600 $O/bench_line.json
+  RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 BV_DP_FORCE_COLLECTIVES=1 timeout 300 python bench.py --full --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-bf16-stream > $O/bench_n512_rccl.json 2> $O/bench_n512_rccl.err; tail -2 $O/bench_n512_rccl.err; cut -c1-300 $O/bench_n512_rccl.json
+  timeout 300 python bench.py --full --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream > $O/bench_n512.json 2> $O/bench_n512.err; cut -c1-300 $O/bench_n512.json
 fi
 if [[ " $* " == *" prof "* ]]; then
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled.json 2> $O/stats.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled.json 2> $O/stats.err
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats512 -- python bench.py --global-batch 512 --steps 4 --warmup 2 --no-cpu-baseline --no-bf16-stream --no-roofline > $O/bench_n512_profiled.json 2> $O/stats512.err
   timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python bench.py --steps 1 --warmup 0 --no-roofline --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/pmc_fetch.json 2> $O/pmc_fetch.err
   timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python bench.py --steps 1 --warmup 0 --no-roofline --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/pmc_write.json 2> $O/pmc_write.err

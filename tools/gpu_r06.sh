@@ -26,10 +26,10 @@ if [[ " $* " == *" tests "* ]]; then
   cp gpurun_out/parity_report.jsonl $O/parity_report.jsonl 2>/dev/null
 fi
 if [[ " $* " == *" bench "* ]]; then
-  timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-700 $O/bench_line.json
+  timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-700 $O/bench_line.json
 fi
 if [[ " $* " == *" prof "* ]]; then
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled.json 2> $O/stats.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled.json 2> $O/stats.err
   find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats.csv
   python tools/trace_family_busy.py $(find $O/stats -name "*kernel_trace.csv" | head -1) > $O/family_busy.json 2> $O/family_busy.err
   rm -rf $O/stats
@@ -41,7 +41,7 @@ if [[ " $* " == *" prof "* ]]; then
 fi
 if [[ " $* " == *" prof1 "* ]]; then
   # per-kernel durations are exclusive only when the towers share one stream: the per-kernel roofline table is built from this trace
-  BV_TOWER_STREAMS=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled_one_stream.json 2> $O/stats1.err
+  BV_TOWER_STREAMS=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-bf16-stream --no-configs --no-live-pmc > $O/bench_line_profiled_one_stream.json 2> $O/stats1.err
   find $O/stats1 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats_one_stream.csv
   rm -rf $O/stats1
   head -16 $O/bench_kernel_stats_one_stream.csv | cut -c1-150
@@ -63,8 +63,8 @@ if [[ " $* " == *" prof_rank "* ]]; then
 fi
 if [[ " $* " == *" rccl3 "* ]]; then
   for ts in 2 1 2 1; do
-    BV_TOWER_STREAMS=$ts RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 BV_DP_FORCE_COLLECTIVES=1 timeout 300 python bench.py --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream --no-live-pmc > $O/bench_n512_rccl_ts$ts.json 2> $O/bench_n512_rccl_ts$ts.err; tail -1 $O/bench_n512_rccl_ts$ts.err; python -c "import json,sys; d=json.load(open('$O/bench_n512_rccl_ts$ts.json')); print('tower_streams', $ts, 'rccl in loop:', round(d['ms_per_step'],2), 'ms', d['roofline']['frac'], d['config']['final_loss'], d.get('rccl'))"
-    BV_TOWER_STREAMS=$ts timeout 300 python bench.py --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream --no-live-pmc > $O/bench_n512_ts$ts.json 2> $O/bench_n512_ts$ts.err; python -c "import json,sys; d=json.load(open('$O/bench_n512_ts$ts.json')); print('tower_streams', $ts, 'no rccl:', round(d['ms_per_step'],2), 'ms', d['roofline']['frac'], d['roofline'].get('stream_overlap_factor'), d['config']['final_loss'])"
+    BV_TOWER_STREAMS=$ts RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 BV_DP_FORCE_COLLECTIVES=1 timeout 300 python bench.py --full --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream --no-live-pmc > $O/bench_n512_rccl_ts$ts.json 2> $O/bench_n512_rccl_ts$ts.err; tail -1 $O/bench_n512_rccl_ts$ts.err; python -c "import json,sys; d=json.load(open('$O/bench_n512_rccl_ts$ts.json')); print('tower_streams', $ts, 'rccl in loop:', round(d['ms_per_step'],2), 'ms', d['roofline']['frac'], d['config']['final_loss'], d.get('rccl'))"
+    BV_TOWER_STREAMS=$ts timeout 300 python bench.py --full --global-batch 512 --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-stream --no-live-pmc > $O/bench_n512_ts$ts.json 2> $O/bench_n512_ts$ts.err; python -c "import json,sys; d=json.load(open('$O/bench_n512_ts$ts.json')); print('tower_streams', $ts, 'no rccl:', round(d['ms_per_step'],2), 'ms', d['roofline']['frac'], d['roofline'].get('stream_overlap_factor'), d['config']['final_loss'])"
   done
 fi
 ls -la $O | head -40

@@ -1031,19 +1031,23 @@ int launch_bwd3(const void* qkv, const void* o, const void* d_o, const float* ls
   }
   int rc = bv_check_launch("bv_attn_bwd(dq)");
   if (rc) return rc;
-  if (g_a4_dkv && KF >= 13) {   // 32-key blocks (A/B: BV_OPT_ATTN_CFG bits 32 = 4 waves x 2 workgroups, 64 = 7 waves x 1)
-    if (g_a4_dkv == 2) {
-      const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)7 * 128 * 4;
-      set_lds(attn4_bwd_dkv_kernel<KF, 7>, sh);
-      hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 7>), dim3(n * H), dim3(7 * 64), sh, s, (const bf16*)qkv,
-                         (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
-    } else {
-      const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)4 * 128 * 4;
-      set_lds(attn4_bwd_dkv_kernel<KF, 4>, sh);
-      hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 4>), dim3(n * H), dim3(4 * 64), sh, s, (const bf16*)qkv,
-                         (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
+  // 32-key blocks (A/B: BV_OPT_ATTN_CFG bits 32 = 4 waves x 2 workgroups, 64 = 7 waves x 1); compile-time KF guard: the
+  // 4-fragment sequences (L <= 64) always take the classic kernel, so no attn4 instantiation exists for them
+  if constexpr (KF >= 13) {
+    if (g_a4_dkv) {
+      if (g_a4_dkv == 2) {
+        const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)7 * 128 * 4;
+        set_lds(attn4_bwd_dkv_kernel<KF, 7>, sh);
+        hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 7>), dim3(n * H), dim3(7 * 64), sh, s, (const bf16*)qkv,
+                           (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
+      } else {
+        const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)4 * 128 * 4;
+        set_lds(attn4_bwd_dkv_kernel<KF, 4>, sh);
+        hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 4>), dim3(n * H), dim3(4 * 64), sh, s, (const bf16*)qkv,
+                           (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
+      }
+      return bv_check_launch("bv_attn_bwd(dkv32)");
     }
-    return bv_check_launch("bv_attn_bwd(dkv32)");
   }
   const size_t sh2 = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)NW2 * 128 * 4;
   set_lds(attn3_bwd_dkv_kernel<KF, NW2, WPS2>, sh2);

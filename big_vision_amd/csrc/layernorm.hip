@@ -622,8 +622,8 @@ extern "C" int bv_layernorm_bwd_bf16x(const void* dy, int dy_is_f32, const void*
   hipLaunchKernelGGL((ln_bwd_bfx_kernel<F32, NV>), dim3(grid), dim3(256), shmem, (hipStream_t)stream, dy,     \
                      (const bf16*)x_bf16, scale, mean, rstd, (const bf16*)dres_bf16, (bf16*)dx_bf16, dscale,  \
                      dbias, dx_colsum, rows, D, row_stride, row_offset)
-  if (dy_is_f32) { if (nv == 2) BV_LN_BWDX(true, 2); else BV_LN_BWDX(true, MAXV8); }
-  else { if (nv == 2) BV_LN_BWDX(false, 2); else BV_LN_BWDX(false, MAXV8); }
+  // (a bf16 dy returned above through the two-row kernel: only the fp32-dy instantiations exist)
+  if (nv == 2) BV_LN_BWDX(true, 2); else BV_LN_BWDX(true, MAXV8);
 #undef BV_LN_BWDX
   return bv_check_launch("bv_layernorm_bwd_bf16x");
 }

@@ -83,6 +83,7 @@ PROTOTYPES = {
     "bv_sqnorm": [P, c_long, P, P],
     "bv_adam_step": [P, P, P, c_int, P, P, P, P, c_long, P, c_int, P, c_float, c_float, c_float,
                      c_float, c_float, c_float, P, P],
+    "bv_trace_step": [P, P, P, c_int, P, P, P, c_long, P, c_int, P, c_float, c_float, c_int, P, P],
 }
 
 PROTOTYPES["bv_adafactor_leaf"] = [P, P, P, c_int, P, P, P, c_int, P, c_float, c_float, c_float, c_float,

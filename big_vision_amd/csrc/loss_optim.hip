@@ -377,7 +377,13 @@ struct AdamArgs {
   float clip_norm, b1, b2, eps, bc1, bc2;
   int mu_bf16;
   float sched[BV_MAX_SCHED];
+  // the optimizer stage of the chain, uniform over the launch (bv_adam_step: OPT_ADAM; bv_trace_step: OPT_TRACE with
+  // mu = the trace, or OPT_IDENTITY without one); beta / nesterov are optax.trace's decay / nesterov
+  int kind;
+  float beta;
+  int nesterov;
 };
+enum { OPT_ADAM = 0, OPT_TRACE = 1, OPT_IDENTITY = 2 };
 
 // Streaming accesses of the optimizer pass: master weights, gradients and moments are each touched once per step
 // and are far larger than any cache (the bf16 shadow is what the next forward reads: plain stores).
@@ -400,8 +406,13 @@ __device__ __forceinline__ void stnt2(uint32_t* p, const uint2& v) {
   __builtin_nontemporal_store(t, reinterpret_cast<u32x2_nt*>(p));
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, long nchunks) {
-  __shared__ double shd[2][256];
+// One optimizer stage of the chain per KIND, the rest (clip, lr, lr_mults, decoupled wd, schedule, sign, apply,
+// bf16 shadow, l2 statistics) shared.  The kind is uniform over the launch, so the kernel branches once at entry and
+// each body is its own straight-line stream: OPT_ADAM is the unchanged Adam body; OPT_TRACE (optax.trace) reads and
+// writes the trace through `mu` and never touches `nu`; OPT_IDENTITY (optax.identity = big_vision.sgd) touches
+// neither (both may be NULL).
+template <int KIND>
+__device__ __forceinline__ void opt_chain(const AdamArgs& a, long nchunks, double (*shd)[256]) {
   float clip = 1.f;
   if (a.clip_norm > 0.f) {
     const float gn = (float)sqrt(*a.gsq);
@@ -418,23 +429,35 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, long nchunks) {
     const long i = c * 1024 + threadIdx.x * 4;
     const float4 p4 = ldnt4(a.p + i);
     const float4 g4 = ldnt4(a.g + i);
-    const float4 v4 = ldnt4(a.nu + i);
-    float m[4];
-    if (a.mu_bf16) {
-      const uint2 u = ldnt2(reinterpret_cast<const uint32_t*>(reinterpret_cast<const bf16*>(a.mu) + i));
-      m[0] = bflo(u.x); m[1] = bfhi(u.x); m[2] = bflo(u.y); m[3] = bfhi(u.y);
-    } else {
-      const float4 m4 = ldnt4(reinterpret_cast<const float*>(a.mu) + i);
-      m[0] = m4.x; m[1] = m4.y; m[2] = m4.z; m[3] = m4.w;
+    float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (KIND == OPT_ADAM) v4 = ldnt4(a.nu + i);
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+    if (KIND != OPT_IDENTITY) {
+      if (a.mu_bf16) {
+        const uint2 u = ldnt2(reinterpret_cast<const uint32_t*>(reinterpret_cast<const bf16*>(a.mu) + i));
+        m[0] = bflo(u.x); m[1] = bfhi(u.x); m[2] = bflo(u.y); m[3] = bfhi(u.y);
+      } else {
+        const float4 m4 = ldnt4(reinterpret_cast<const float*>(a.mu) + i);
+        m[0] = m4.x; m[1] = m4.y; m[2] = m4.z; m[3] = m4.w;
+      }
     }
     float p[4] = {p4.x, p4.y, p4.z, p4.w};
     const float g[4] = {g4.x * clip, g4.y * clip, g4.z * clip, g4.w * clip};
     float v[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      m[e] = a.b1 * m[e] + (1.f - a.b1) * g[e];
-      v[e] = a.b2 * v[e] + (1.f - a.b2) * g[e] * g[e];
-      float u = (m[e] / a.bc1) / (sqrtf(v[e] / a.bc2) + a.eps);
+      float u;
+      if (KIND == OPT_ADAM) {
+        m[e] = a.b1 * m[e] + (1.f - a.b1) * g[e];
+        v[e] = a.b2 * v[e] + (1.f - a.b2) * g[e] * g[e];
+        u = (m[e] / a.bc1) / (sqrtf(v[e] / a.bc2) + a.eps);
+      } else if (KIND == OPT_TRACE) {
+        // optax.trace: t' = g + decay t (t as stored, fp32 math); nesterov: g + decay t' on the UNROUNDED t'
+        m[e] = g[e] + a.beta * m[e];
+        u = a.nesterov ? g[e] + a.beta * m[e] : m[e];
+      } else {
+        u = g[e];
+      }
       u = hp.lr_eff * u + hp.wd_eff * p[e];
       u *= sched;
       p[e] -= u;
@@ -444,14 +467,16 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, long nchunks) {
     sp += (double)cp;
     su += (double)cu;
     stnt4(a.p + i, make_float4(p[0], p[1], p[2], p[3]));
-    stnt4(a.nu + i, make_float4(v[0], v[1], v[2], v[3]));
-    if (a.mu_bf16) {
-      uint2 u;
-      u.x = pack_bf2(m[0], m[1]);
-      u.y = pack_bf2(m[2], m[3]);
-      stnt2(reinterpret_cast<uint32_t*>(reinterpret_cast<bf16*>(a.mu) + i), u);
-    } else {
-      stnt4(reinterpret_cast<float*>(a.mu) + i, make_float4(m[0], m[1], m[2], m[3]));
+    if (KIND == OPT_ADAM) stnt4(a.nu + i, make_float4(v[0], v[1], v[2], v[3]));
+    if (KIND != OPT_IDENTITY) {
+      if (a.mu_bf16) {
+        uint2 u;
+        u.x = pack_bf2(m[0], m[1]);
+        u.y = pack_bf2(m[2], m[3]);
+        stnt2(reinterpret_cast<uint32_t*>(reinterpret_cast<bf16*>(a.mu) + i), u);
+      } else {
+        stnt4(reinterpret_cast<float*>(a.mu) + i, make_float4(m[0], m[1], m[2], m[3]));
+      }
     }
     if (a.shadow) {
       uint2 u;
@@ -470,6 +495,16 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, long nchunks) {
       atomicAdd(a.stats + threadIdx.x, t);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, long nchunks) {
+  __shared__ double shd[2][256];
+  if (a.kind == OPT_TRACE)
+    opt_chain<OPT_TRACE>(a, nchunks, shd);
+  else if (a.kind == OPT_IDENTITY)
+    opt_chain<OPT_IDENTITY>(a, nchunks, shd);
+  else
+    opt_chain<OPT_ADAM>(a, nchunks, shd);
 }
 
 }  // namespace
@@ -568,8 +603,29 @@ extern "C" int bv_adam_step(float* params, const float* grads, void* mu, int mu_
   a.segs = segs; a.chunk_seg = chunk_seg; a.gsq = gsq; a.stats = stats;
   a.clip_norm = clip_norm; a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2;
   a.mu_bf16 = mu_bf16;
+  a.kind = OPT_ADAM; a.beta = 0.f; a.nesterov = 0;
   const long nchunks = count / 1024;
   const unsigned grid = (unsigned)(nchunks < 4096 ? nchunks : 4096);   // 16 workgroups per CU
   hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, nchunks);
   return bv_check_launch("bv_adam_step");
+}
+
+extern "C" int bv_trace_step(float* params, const float* grads, void* trace, int trace_bf16, void* shadow_bf16,
+                             const bv_adam_seg* segs, const int* chunk_seg, long count, const float* sched, int nsched,
+                             const double* gsq, float clip_norm, float momentum, int nesterov, double* stats,
+                             void* stream) {
+  BV_REQUIRE(count > 0 && count % 1024 == 0, "bv_trace_step: count=%ld must be a positive multiple of 1024", count);
+  BV_REQUIRE(clip_norm <= 0.f || gsq != nullptr, "bv_trace_step: clipping needs gsq");
+  BV_REQUIRE(sched != nullptr && nsched >= 1 && nsched <= BV_MAX_SCHED, "bv_trace_step: 1..%d schedule values required", BV_MAX_SCHED);
+  AdamArgs a;
+  for (int i = 0; i < BV_MAX_SCHED; ++i) a.sched[i] = i < nsched ? sched[i] : 0.f;
+  a.p = params; a.g = grads; a.mu = trace; a.nu = nullptr; a.shadow = (bf16*)shadow_bf16;
+  a.segs = segs; a.chunk_seg = chunk_seg; a.gsq = gsq; a.stats = stats;
+  a.clip_norm = clip_norm; a.b1 = a.b2 = a.eps = 0.f; a.bc1 = a.bc2 = 1.f;
+  a.mu_bf16 = trace_bf16 != 0;
+  a.kind = trace ? OPT_TRACE : OPT_IDENTITY; a.beta = momentum; a.nesterov = nesterov != 0;
+  const long nchunks = count / 1024;
+  const unsigned grid = (unsigned)(nchunks < 4096 ? nchunks : 4096);
+  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, nchunks);
+  return bv_check_launch("bv_trace_step");
 }

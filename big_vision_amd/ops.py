@@ -637,6 +637,17 @@ def adam_step_(params, grads, mu, nu, shadow, segs, chunk_seg, count, sched, gsq
             _p(stats), _stream())
 
 
+def trace_step_(params, grads, trace, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, momentum, nesterov,
+                stats):
+  """The fused chain with optax.trace (trace: bf16 or fp32 accumulator) or, trace=None, optax.identity
+  (bv_trace_step); segs / chunk_seg / sched as adam_step_."""
+  import ctypes
+  arr = (ctypes.c_float * len(sched))(*[float(v) for v in sched])
+  _lib.call("bv_trace_step", _p(params), _p(grads), _p(trace), int(trace is not None and trace.dtype == BF16),
+            _p(shadow), _p(segs), _p(chunk_seg), count, ctypes.cast(arr, ctypes.c_void_p), len(sched), _p(gsq),
+            float(clip_norm or 0.0), float(momentum), int(bool(nesterov)), _p(stats), _stream())
+
+
 def adafactor_leaf_(params, grads, momentum, shadow, view, state, factored, gsq, clip_norm, decay, eps, mom,
                     lr_eff, wd, sched, stats):
   """One leaf of the fused Adafactor step (bv_adafactor_leaf); view: ctypes array of 9 longs (host)."""

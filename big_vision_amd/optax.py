@@ -9,7 +9,9 @@ regex semantics (utils.py:1195-1212).  The chain
   add_decayed_weights -> scale_by_schedule / set_to_zero(frozen) -> scale(-1)
   -> optax.apply_updates
 
-runs as bv_sqnorm + bv_adam_step over the flat parameter buffer.  Frozen
+runs as bv_sqnorm + bv_adam_step over the flat parameter buffer;
+big_vision.momentum_hp (optax.trace) and big_vision.sgd (optax.identity) run the
+same chain through bv_trace_step.  Frozen
 parameters (schedule None) live past the trainable prefix of the store: no
 gradient, no Adam state (optax_test.py:301-318), excluded from the clip norm
 (optax.py:105) and from l2_grads (trainers/proj/image_text/siglip.py:316).
@@ -28,6 +30,25 @@ from big_vision_amd.params import ParamStore, make_masks
 
 MAX_SCHED = 8
 ADAFACTOR_NAMES = ("big_vision.scale_by_adafactor", "scale_by_adafactor")
+TRACE_NAMES = ("big_vision.momentum_hp", "big_vision.sgd")
+
+
+def _trace_hparams(name, okw):
+  """(momentum, accumulator dtype, nesterov) of big_vision.momentum_hp (optax.py:219-224: optax.trace(decay=momentum,
+  accumulator_dtype=dtype, nesterov=nesterov)), or None for big_vision.sgd (optax.py:227: optax.identity, which takes
+  no arguments).  Unknown keys are refused as calling the reference's factory with them would be."""
+  allowed = ("momentum", "dtype", "nesterov") if name == "big_vision.momentum_hp" else ()
+  unknown = sorted(set(okw) - set(allowed))
+  if unknown:
+    raise TypeError(f"{name}() got unexpected keyword argument(s) {unknown} (accepted: {list(allowed)})")
+  if name == "big_vision.sgd":
+    return None
+  dt = okw.get("dtype", "bfloat16")
+  dts = {"bfloat16": torch.bfloat16, "torch.bfloat16": torch.bfloat16, "float32": torch.float32,
+         "torch.float32": torch.float32}
+  if str(dt) not in dts:
+    raise ValueError(f"{name}: accumulator dtype {dt!r} is not supported (bfloat16 or float32)")
+  return float(okw.get("momentum", 0.9)), dts[str(dt)], bool(okw.get("nesterov", False))
 
 
 
@@ -154,10 +175,14 @@ class Optimizer:
       assert okw.get("eps_root", 0.0) == 0.0, "eps_root is not supported"
       mu_dtype = okw.get("mu_dtype")
       mu_dtype = torch.bfloat16 if str(mu_dtype) in ("bfloat16", "torch.bfloat16") else torch.float32
+    elif self.name in TRACE_NAMES:
+      hp = _trace_hparams(self.name, okw)
+      self.momentum, mu_dtype, self.nesterov = hp if hp is not None else (0.0, None, False)
     elif self.name in ADAFACTOR_NAMES:
       self.clip_norm = float(config.get("grad_clip_norm") or 0.0)
       _refuse_per_example_clip(config)
       self.lr = float(config["lr"])
+      self.kind = "adafactor"
       self._init_adafactor(okw, lr_mult, wd, sched_idx_of_leaf)
       # "fsdp": the PARAMETERS are sharded too, as under Adam - by OWNERSHIP of whole tensors here (the factored
       # statistics are per tensor): the store keeps the fp32 master of this rank's run of entries plus the replicated
@@ -168,8 +193,10 @@ class Optimizer:
         store.shard_master_(self.lo, self.hi, 0, self.comm, bounds=self.bounds)
       return
     else:
-      raise NotImplementedError(f"optax_name={self.name!r}: scale_by_adam and big_vision.scale_by_adafactor "
-                                "are on the fused path")
+      raise NotImplementedError(f"optax_name={self.name!r}: scale_by_adam, big_vision.scale_by_adafactor, "
+                                "big_vision.momentum_hp and big_vision.sgd are on the fused path")
+    # the optimizer stage of bv_adam_step's chain: Adam moments mu / nu, the trace of momentum_hp in mu, or no state
+    self.kind = "adam" if self.name == "scale_by_adam" else ("trace" if mu_dtype is not None else "identity")
     self.clip_norm = float(config.get("grad_clip_norm") or 0.0)
     _refuse_per_example_clip(config)
     self.lr = float(config["lr"])
@@ -204,8 +231,8 @@ class Optimizer:
       n_own = self.S
     else:
       self.lo, self.hi, n_own = 0, n_tr, n_tr
-    self.mu = torch.zeros(n_own, device=dev, dtype=mu_dtype)
-    self.nu = torch.zeros(n_own, device=dev, dtype=torch.float32)
+    self.mu = torch.zeros(n_own, device=dev, dtype=mu_dtype) if self.kind != "identity" else None
+    self.nu = torch.zeros(n_own, device=dev, dtype=torch.float32) if self.kind == "adam" else None
     # "fsdp": the PARAMETERS are sharded too (reference sharding.py:104-139) - the store keeps this rank's slice of the
     # fp32 master plus the replicated entries from here on (ParamStore.shard_master_); config.fsdp_shard_params = False
     # keeps the round-4 form (state and update sharded, fp32 master replicated)
@@ -489,7 +516,7 @@ class Optimizer:
     if self.name in ADAFACTOR_NAMES:
       return self._adafactor_step()
     if self.sharded:
-      return self._sharded_adam_step()
+      return self._sharded_step()
     st = self.store
     n_tr = st.trainable_count
     k = self.count
@@ -497,9 +524,7 @@ class Optimizer:
     self.gsq.zero_()
     ops.sqnorm_(st.grad, self.gsq)
     self.stats.zero_()
-    ops.adam_step_(st.master, st.grad, self.mu, self.nu, st.shadow, self.segs, self.chunk_seg, n_tr,
-                   sched, self.gsq, self.clip_norm, self.b1, self.b2, self.eps,
-                   1.0 - self.b1 ** (k + 1), 1.0 - self.b2 ** (k + 1), self.stats)
+    self._launch(st.master, st.grad, self.mu, self.nu, st.shadow, self.chunk_seg, n_tr, sched, k)
     self.count = k + 1
     st.shadow_version += 1     # the kernel refreshed the bf16 shadow of the trainable prefix
     return {"l2_grads": torch.sqrt(self.gsq[0]),
@@ -536,16 +561,25 @@ class Optimizer:
       self.grad_sync().finish()
     self._reduced_for = None      # the stamp is good for ONE step
 
-  def _sharded_adam_step(self):
+  def _launch(self, master, grad, mu, nu, shadow, chunk_seg, n, sched, k):
+    """The fused chain over n elements: bv_adam_step, or bv_trace_step for momentum_hp (mu = the trace) and sgd."""
+    if self.kind == "adam":
+      ops.adam_step_(master, grad, mu, nu, shadow, self.segs, chunk_seg, n, sched, self.gsq, self.clip_norm,
+                     self.b1, self.b2, self.eps, 1.0 - self.b1 ** (k + 1), 1.0 - self.b2 ** (k + 1), self.stats)
+    else:
+      ops.trace_step_(master, grad, mu, shadow, self.segs, chunk_seg, n, sched, self.gsq, self.clip_norm,
+                      self.momentum, self.nesterov, self.stats)
+
+  def _sharded_step(self):
     """"fsdp" placement.  The trainer has summed every gradient range onto its OWNER during the backward
     (grad_sync() / dp.GradShardSync, overlapped with the remaining GEMMs like the all-reduce of the replicated
     path): st.grad[lo:hi] is this rank's slice of the global gradient, in place.  Then: global clip norm from the
-    slices' square norms -> the fused Adam kernel on the slice (same kernel, same per-chunk hyper-parameter table,
+    slices' square norms -> the fused optimizer kernel (Adam, trace or identity) on the slice (same kernel, same per-chunk hyper-parameter table,
     offset pointers; it also refreshes the bf16 shadow of the slice) -> in-place exchange of the updated fp32
     slices -> bf16 shadow of the slices this rank does NOT own (two casts: the frozen tail and the own slice are
     left alone, static_version does not move, so transposed images of frozen towers are not rebuilt - advisor r3).
     Per step and rank this moves (N-1)/N x 4 B x P each way - the bytes of the all-reduce it replaces - runs 1/N
-    of the optimizer kernel and holds 1/N of its state; no staging copies."""
+    of the optimizer kernel and holds 1/N of its state (moments or trace); no staging copies."""
     st, comm = self.store, self.comm
     n_tr, S, lo, hi = st.trainable_count, self.S, self.lo, self.hi
     n_own = hi - lo
@@ -559,9 +593,9 @@ class Optimizer:
     self.stats.zero_()
     master_slice = st.master_own[:n_own] if st.master_sharded else st.master[lo:hi]
     if n_own:
-      ops.adam_step_(master_slice, st.grad[lo:hi], self.mu[:n_own], self.nu[:n_own], st.shadow[lo:hi], self.segs,
-                     self.chunk_seg[lo // 1024:], n_own, sched, self.gsq, self.clip_norm, self.b1, self.b2, self.eps,
-                     1.0 - self.b1 ** (k + 1), 1.0 - self.b2 ** (k + 1), self.stats)
+      own = lambda t: None if t is None else t[:n_own]
+      self._launch(master_slice, st.grad[lo:hi], own(self.mu), own(self.nu), st.shadow[lo:hi],
+                   self.chunk_seg[lo // 1024:], n_own, sched, k)
     comm.all_reduce_scalars_(self.stats)
     self.count = k + 1
     if st.master_sharded:
@@ -630,13 +664,19 @@ class Optimizer:
     i_opt, i_sched = self._chain_layout()
     cnt = np.asarray(self.count, np.int32)
     tree = {str(j): {"0": {"0": cnt}} for j in i_sched}
-    tree[str(i_opt)] = {"0": self._opt_state_tree(cnt)}
+    opt_tree = self._opt_state_tree(cnt)
+    if opt_tree:      # optax.identity (big_vision.sgd): EmptyState, no names
+      tree[str(i_opt)] = {"0": opt_tree}
     return tree
 
   def _opt_state_tree(self, cnt):
     if self.name in ADAFACTOR_NAMES:
       self._gather_af_state()
       return self._af_state_tree(cnt)
+    if self.kind == "trace":     # TraceState(trace)
+      return {"0": self._moment_tree(self._full_moment(self.mu))}
+    if self.kind == "identity":
+      return {}
     return {"0": cnt, "1": self._moment_tree(self._full_moment(self.mu)), "2": self._moment_tree(self._full_moment(self.nu))}
 
   def _trainable_ext_names(self):
@@ -692,7 +732,16 @@ class Optimizer:
   def load_state_tree(self, tree):
     """Inverse of `state_tree` (accepts the flat `{name: array}` form too)."""
     flat = dict(u.tree_flatten_with_names(tree)[0])   # flat '/'-joined keys pass through unchanged
-    i_opt, _ = self._chain_layout()
+    i_opt, i_sched = self._chain_layout()
+    if self.name in TRACE_NAMES:
+      # TraceState / EmptyState keep no count: the step count is scale_by_schedule's (get_count, optax.py:30-41)
+      keys = [f"{j}/0/0" for j in i_sched if f"{j}/0/0" in flat]
+      if not keys:
+        raise ValueError(f"optimizer state holds no schedule count (expected one of {[f'{j}/0/0' for j in i_sched]})")
+      self.count = int(np.asarray(flat[keys[0]]))
+      if self.kind == "trace":
+        self._load_moment(self.mu, flat, f"{i_opt}/0/0/")
+      return
     self._load_opt_state(flat, f"{i_opt}/0/")
 
   def _assign_moment(self, flat_buf, flat, prefix):
@@ -715,6 +764,16 @@ class Optimizer:
         if tuple(src.shape) != tuple(dst.shape):
           raise ValueError(f"Shape mismatch for optimizer state {key}: {tuple(src.shape)} vs {tuple(dst.shape)}")
         dst.copy_(src.to(dst.dtype).to(dst.device))
+
+  def _load_moment(self, buf, flat, prefix):
+    """Whole-model moment `prefix<leaf>` of a checkpoint into buf (its own slice under the "fsdp" placement)."""
+    if not self.sharded:
+      self._assign_moment(buf, flat, prefix)
+      return
+    full = torch.zeros(self.store.trainable_count, device=buf.device, dtype=buf.dtype)
+    self._assign_moment(full, flat, prefix)
+    buf.zero_()
+    buf[:self.hi - self.lo] = full[self.lo:self.hi]
 
   def _load_opt_state(self, flat, pre):
     if self.name in ADAFACTOR_NAMES:
@@ -763,6 +822,8 @@ class Optimizer:
     if self.name in ADAFACTOR_NAMES:
       self._gather_af_state()
       return {"mu": self._full_mu(), "af_state": self.af_state, "count": self.count}
+    if self.kind != "adam":   # momentum_hp: the trace (whole, as below); sgd: the count alone
+      return {"trace": self._full_moment(self.mu) if self.mu is not None else None, "count": self.count}
     # always moments of exactly `trainable_count` elements, whatever the placement (advisor r5: a sharded
     # optimizer on an inactive one-rank group used to hand out its padded own-slice buffers)
     if self.sharded:
@@ -780,6 +841,18 @@ class Optimizer:
         else:
           self.mu.copy_(d["mu"].to(self.mu.dtype))
       self.af_state.copy_(d["af_state"]); self.count = int(d["count"])
+      return
+    if self.kind != "adam":
+      if self.mu is not None:
+        t, n_tr = d["trace"], self.store.trainable_count
+        if t is None or t.numel() != n_tr:
+          raise ValueError(f"trace of {None if t is None else t.numel()} elements does not fit this model's {n_tr} "
+                           "trainable parameters (state_dict() of any placement holds the whole trace)")
+        if self.sharded:
+          self._set_own_mu(t.to(self.mu.device))
+        else:
+          self.mu.copy_(t.to(self.mu.dtype))
+      self.count = int(d["count"])
       return
     mu, nu = d["mu"], d["nu"]
     n_tr = self.store.trainable_count

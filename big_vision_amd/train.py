@@ -22,6 +22,7 @@ reference's shard_map (:283-289).
 from __future__ import annotations
 
 import importlib
+import os
 
 import torch
 
@@ -70,6 +71,8 @@ def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_step
       frozen.add(e.name)
   store = ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
   store.init_random(_seed_of(rng))
+  if config.get("model_init"):
+    _load_model_init(model, config, store)
   store.refresh_shadow()
   store.want_grads = True
   from big_vision_amd import sharding     # train.py:201-203: replicate, or fsdp = sharded optimizer state / update
@@ -79,6 +82,25 @@ def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_step
   opt, sched_fns = bv_optax.make(config, store, sched_kw=dict(total_steps=total_steps, batch_size=batch_size,
                                                                data_size=None), comm=comm, shard=fsdp)
   return {"params": store.tree(), "opt": opt}, sched_fns
+
+
+def _load_model_init(model, config, store):
+  """train.py:353-359: `model_mod.load(params, config.model_init, config.model, **config.model_load)` into the store.
+  Runs before bv_optax.make: the fsdp placement shards the fp32 master there, and a load after it would leave the
+  shadow and master views of the earlier layout behind."""
+  model_mod = importlib.import_module(type(model).__module__)
+  if not hasattr(model_mod, "load"):
+    raise NotImplementedError(f"config.model_init: {model_mod.__name__} has no load()")
+  init = config.model_init
+  path = getattr(model_mod, "VANITY_NAMES", {}).get(init, init) if isinstance(init, str) else init
+  if isinstance(path, str) and "://" in path:
+    raise FileNotFoundError(f"config.model_init={init!r} resolves to {path!r}: remote checkpoints cannot be opened "
+                            "here; download it and pass the local .npz path")
+  if isinstance(path, str) and not any(os.path.isfile(p) for p in (path, path.rsplit(":", 1)[0])):
+    raise FileNotFoundError(f"config.model_init={init!r}: no such checkpoint file (remote vanity names are not "
+                            "fetched; pass the local .npz path)")
+  params = model_mod.load(store.tree(), init, config.get("model"), **config.get("model_load", {}))
+  store.load_tree(params)
 
 
 def loss_fn(model, params, images, labels, config, comm=None):

@@ -426,6 +426,20 @@ int bv_adam_step(float* params, const float* grads, void* mu, int mu_bf16, float
                  float clip_norm, float b1, float b2, float eps, float bc1, float bc2,
                  double* stats, void* stream);
 
+/* The same fused chain with optax.trace (SGD-momentum) or optax.identity as the
+ * optimizer stage: big_vision.momentum_hp = optax.trace(decay=momentum,
+ * accumulator_dtype=bfloat16, nesterov=False) and big_vision.sgd =
+ * optax.identity (optax.py:219-227).  Per element, with c the clip factor from
+ * gsq as in bv_adam_step: g' = c g, t' = g' + momentum t (t read as stored,
+ * fp32 math), o = nesterov ? g' + momentum t' : t' (the unrounded t'), t'
+ * stored as bf16 (trace_bf16=1) or fp32; then lr_eff, wd_eff, schedule, sign,
+ * apply, shadow and stats exactly as bv_adam_step.  trace == NULL selects
+ * identity (o = g', no state).  No second moment is read or written. */
+int bv_trace_step(float* params, const float* grads, void* trace, int trace_bf16, void* shadow_bf16,
+                  const bv_adam_seg* segs, const int* chunk_seg, long count,
+                  const float* sched /*host, nsched values*/, int nsched, const double* gsq,
+                  float clip_norm, float momentum, int nesterov, double* stats, void* stream);
+
 /* One parameter LEAF of the BigVision Adafactor step (big_vision/optax.py:187-216:
  * scale_by_factored_rms(decay 1 - t^-0.8 capped at 0.999, min_dim_size_to_factor 32, eps 1e-30) ->
  * ema(0.9, debias=False, bf16 accumulator)) fused with the rest of the bv_optax chain

@@ -8,6 +8,8 @@ staging race shows up as run-to-run differences) and match the general
 import pytest
 import torch
 
+import _bounds as B
+
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -49,15 +51,15 @@ def test_nt_matches_reference(dev, fast, M, N, K):
   a = rnd((M, K), dev, 1, dtype=BF16)
   b = rnd((N, K), dev, 2, 0.05, dtype=BF16)
   bias = rnd((N,), dev, 3)
-  ref = a.float() @ b.float().T + bias
+  ref = a.double() @ b.double().T + bias.double()
   outs = [ops.gemm(a, b, a_kmajor=True, b_kmajor=True, bias=bias, out_dtype=F32) for _ in range(4)]
-  close(outs[0], ref, 1e-4, 2e-3, "nt f32")
+  B.check_gemm(outs[0], ref, a, b.T, legacy=(1e-4, 2e-3), name="nt f32")
   for o in outs[1:]:
     assert torch.equal(o, outs[0]), "run-to-run difference (staging race?)"
   gen = _general(lambda: ops.gemm(a, b, a_kmajor=True, b_kmajor=True, bias=bias, out_dtype=F32))
   close(outs[0], gen, 1e-5, 1e-3, "nt vs general kernel")
   o16 = ops.gemm(a, b, a_kmajor=True, b_kmajor=True, bias=bias, out_dtype=BF16)
-  close(o16, ref, 1e-2, 1e-2, "nt bf16")
+  B.check_gemm(o16, ref, a, b.T, legacy=(1e-2, 1e-2), name="nt bf16")
 
 
 def test_nt_epilogues(dev, fast):
@@ -66,34 +68,36 @@ def test_nt_epilogues(dev, fast):
   x = rnd((M, K), dev, 8, dtype=BF16)
   w = rnd((N, K), dev, 9, 0.1, dtype=BF16)
   b = rnd((N,), dev, 10)
-  pre = x.float() @ w.float().T + b
+  pre = x.double() @ w.double().T + b.double()
   res = rnd((M, N), dev, 11)
   kw = dict(a_kmajor=True, b_kmajor=True)
+  wt = w.T
   y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=res, **kw)
-  close(y, pre + res, 1e-4, 2e-3, "residual")
+  B.check_gemm(y, pre + res.double(), x, wt, legacy=(1e-4, 2e-3), name="residual", n_adds=2)
   # bf16 residual stream: aux and C are bf16 (same epilogue id, out_f32 = 0)
   resb = res.to(BF16)
   yb = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_RESIDUAL, aux=resb, **kw)
-  close(yb, pre + resb.float(), 1e-2, 1e-2, "residual (bf16 stream)")
+  B.check_gemm(yb, pre + resb.double(), x, wt, legacy=(1e-2, 1e-2), name="residual (bf16 stream)", n_adds=2)
   assert torch.equal(yb, ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_RESIDUAL, aux=resb, **kw))
   pos = rnd((L, N), dev, 12)
   y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_POS, aux=pos, aux_rows=L, **kw)
-  close(y, pre + pos.repeat(M // L, 1), 1e-4, 2e-3, "pos")
+  B.check_gemm(y, pre + pos.double().repeat(M // L, 1), x, wt, legacy=(1e-4, 2e-3), name="pos", n_adds=2)
   g = torch.empty((M, N), device=dev, dtype=BF16)
   h = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_GELU, out2=g, **kw)
-  close(h, pre, 1e-2, 1e-2, "gelu pre")
-  close(g, torch.nn.functional.gelu(pre, approximate="tanh"), 1e-2, 1e-2, "gelu out")
+  B.check_gemm(h, pre, x, wt, legacy=(1e-2, 1e-2), name="gelu pre")
+  close(g, B.gelu_tanh64(pre), 1e-2, 1e-2, "gelu out")
+  B.check_gelu_g(g, h, legacy=(1e-2, 1e-2), name="gelu out (of the stored h)")
   hh = rnd((M, N), dev, 15, dtype=BF16)
   hf = hh.float().requires_grad_(True)
   torch.nn.functional.gelu(hf, approximate="tanh").sum().backward()
-  ref = (x.float() @ w.float().T) * hf.grad
+  ref = (x.double() @ w.double().T) * B.dgelu_tanh64(hh)
   out = ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_GELU_BWD, aux=hh, **kw)
-  close(out, ref, 1e-2, 2e-2, "gelu bwd")
+  B.check_gelu_bwd(out, x, wt, hh, legacy=(1e-2, 2e-2), name="gelu bwd")
   # GELU_BWD_EMIT: same dX, and C2 = gelu(aux) with the bits the forward epilogue produces
   g2 = torch.empty((M, N), device=dev, dtype=BF16)
   out2 = ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_GELU_BWD_EMIT, aux=hh, out2=g2, **kw)
-  close(out2, ref, 1e-2, 2e-2, "gelu bwd (emit)")
-  close(g2, torch.nn.functional.gelu(hh.float(), approximate="tanh"), 1e-2, 1e-2, "emitted gelu")
+  B.check_gelu_bwd(out2, x, wt, hh, legacy=(1e-2, 2e-2), name="gelu bwd (emit)")
+  B.check_gelu_g(g2, hh, legacy=(1e-2, 1e-2), name="emitted gelu")
   g3 = torch.empty((M, N), device=dev, dtype=BF16)
   ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_GELU_BWD_EMIT, aux=h, out2=g3, **kw)
   assert torch.equal(g3, g), "gelu(h) re-emitted by the backward differs from the forward's"
@@ -110,10 +114,10 @@ def test_nt_epilogues(dev, fast):
   d4 = torch.empty((M, N), device=dev, dtype=BF16)
   ret = ops.gemm(x, w, bias=b, out=g4, epilogue=ops.EPI_GELU_GD, out2=d4, **kw)
   assert ret is g4
-  pf = pre.detach().clone().requires_grad_(True)
-  torch.nn.functional.gelu(pf, approximate="tanh").sum().backward()
-  close(g4, torch.nn.functional.gelu(pre, approximate="tanh"), 1e-2, 1e-2, "gelu_gd value")
-  close(d4, pf.grad, 1e-2, 1e-2, "gelu_gd derivative")
+  close(g4, B.gelu_tanh64(pre), 1e-2, 1e-2, "gelu_gd value")
+  close(d4, B.dgelu_tanh64(pre), 1e-2, 1e-2, "gelu_gd derivative")
+  B.check_gelu_g(g4, h, legacy=(1e-2, 1e-2), name="gelu_gd value (of bf16(pre))")
+  B.check_gelu_dg(d4, h, legacy=(1e-2, 1e-2), name="gelu_gd derivative (of bf16(pre))")
   # one definition of the activation for every context kind: GELU_GD's g has the bits of GELU's g, and
   # MUL fed GELU_GD's derivative reproduces GELU_BWD / GELU_BWD_EMIT fed the stored h, bit for bit
   assert torch.equal(g4, g), "GELU_GD and GELU disagree on gelu(h)"
@@ -125,8 +129,8 @@ def test_nt_epilogues(dev, fast):
   dd = hf.grad.to(BF16)
   cs = torch.ones((N,), device=dev, dtype=F32)
   o5 = ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_MUL, aux=dd, colsum=cs, **kw)
-  ref5 = (x.float() @ w.float().T) * dd.float()
-  close(o5, ref5, 1e-2, 2e-2, "mul")
+  ref5 = (x.double() @ w.double().T) * dd.double()
+  B.check_mul(o5, x, wt, dd, legacy=(1e-2, 2e-2), name="mul")
   close(cs, 1.0 + ref5.sum(0), 1e-3, 1e-3 * ref5.abs().sum(0).max().item(), "mul: fused colsum")
   assert torch.equal(o5, ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_MUL, aux=dd, **kw))
   # the 256x256 kernel and the general kernel evaluate the same operation sequence: same bits
@@ -134,7 +138,7 @@ def test_nt_epilogues(dev, fast):
   _general(lambda: ops.gemm(x, w, bias=b, out=gg, epilogue=ops.EPI_GELU_GD, out2=dg, **kw))
   close(gg, g4, 1e-2, 1e-2, "gelu_gd vs general kernel"); close(dg, d4, 1e-2, 1e-2, "gelu_gd' vs general kernel")
   y = ops.gemm(x, w, out_dtype=BF16, alpha=0.5, **kw)
-  close(y, 0.5 * (x.float() @ w.float().T), 1e-2, 1e-2, "alpha")
+  B.check_gemm(y, 0.5 * (x.double() @ w.double().T), x, wt, legacy=(1e-2, 1e-2), name="alpha", n_adds=0, alpha=0.5)
 
 
 def test_nt_strided_views(dev, fast):
@@ -146,7 +150,7 @@ def test_nt_strided_views(dev, fast):
   cbuf = torch.zeros((M, 2 * N), device=dev, dtype=F32)
   a, b = abuf[:, K:2 * K], bbuf[:, K:]
   ops.gemm(a, b, a_kmajor=True, b_kmajor=True, out=cbuf[:, N:])
-  close(cbuf[:, N:], a.float() @ b.float().T, 1e-4, 2e-3, "strided")
+  B.check_gemm(cbuf[:, N:], a.double() @ b.double().T, a, b.T, legacy=(1e-4, 2e-3), name="strided", n_adds=0)
   assert torch.count_nonzero(cbuf[:, :N]) == 0
 
 
@@ -166,7 +170,7 @@ def test_tn_dw_matches_reference(dev, fast, Din, Dout, T, split):
   for _ in range(3):
     out = base.clone()
     ops.gemm(x, dy, a_kmajor=False, b_kmajor=False, out=out, epilogue=ops.EPI_ATOMIC, split_k=split)
-    close(out, ref, 1e-4, tol, "tn dw")
+    B.check_gemm(out, ref, x.T, dy, legacy=(1e-4, tol), name="tn dw", n_adds=2 + max(split, 1))
   out1 = torch.zeros((Din, Dout), device=dev)
   ops.gemm(x, dy, a_kmajor=False, b_kmajor=False, out=out1, epilogue=ops.EPI_ATOMIC, split_k=1)
   out2 = torch.zeros((Din, Dout), device=dev)
@@ -183,7 +187,7 @@ def test_big_shape_spot_check(dev, fast):
   y = ops.gemm(x, wt, a_kmajor=True, b_kmajor=True, out_dtype=F32)
   rows = torch.arange(0, T, 97, device=dev)
   ref = x[rows].double() @ wt.double().T
-  close(y[rows], ref, 1e-4, 2e-3, "fc1 rows")
+  B.check_gemm(y[rows], ref, x[rows], wt.T, legacy=(1e-4, 2e-3), name="fc1 rows", n_adds=0)
   y2 = ops.gemm(x, wt, a_kmajor=True, b_kmajor=True, out_dtype=F32)
   assert torch.equal(y, y2)
 
@@ -322,6 +326,7 @@ def test_fused_epilogues_multi_tile_vs_fp64(dev, fast, M, N, K, reserve):
   b = rnd((N,), dev, 33)
   kw = dict(a_kmajor=True, b_kmajor=True)
   acc = x.double() @ w.double().T            # fp64 product of the bf16-rounded operands
+  wt = w.T
   pre = acc + b.double()
   res = rnd((M, N), dev, 34, 2.0)
   hh = rnd((M, N), dev, 35, dtype=BF16)       # a stored pre-activation (light contexts)
@@ -331,31 +336,33 @@ def test_fused_epilogues_multi_tile_vs_fp64(dev, fast, M, N, K, reserve):
   old = ctx_.set("gemm_reserve_cus", reserve)
   try:
     # plain +bias (QKV / dX shapes), bf16 and fp32 outputs
-    close(ops.gemm(x, w, bias=b, out_dtype=F32, **kw), pre, 1e-4, 2e-3, "bias f32")
-    close(ops.gemm(x, w, bias=b, out_dtype=BF16, **kw), pre, 1e-2, 1e-2, "bias bf16")
+    B.check_gemm(ops.gemm(x, w, bias=b, out_dtype=F32, **kw), pre, x, wt, legacy=(1e-4, 2e-3), name="bias f32")
+    B.check_gemm(ops.gemm(x, w, bias=b, out_dtype=BF16, **kw), pre, x, wt, legacy=(1e-2, 1e-2), name="bias bf16")
     # +residual on the fp32 stream (the rolling kernel) and on the bf16 stream
     y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=res, **kw)
-    close(y, pre + res.double(), 1e-4, 2e-3, "residual f32")
+    B.check_gemm(y, pre + res.double(), x, wt, legacy=(1e-4, 2e-3), name="residual f32", n_adds=2)
     assert torch.equal(y, ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=res, **kw)), \
         "residual f32: run-to-run difference"
     resb = res.to(BF16)
-    close(ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_RESIDUAL, aux=resb, **kw), pre + resb.double(),
-          1e-2, 2e-2, "residual bf16")
+    B.check_gemm(ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_RESIDUAL, aux=resb, **kw), pre + resb.double(),
+                 x, wt, legacy=(1e-2, 2e-2), name="residual bf16", n_adds=2)
     # + position embedding (stem epilogue): aux row = token row mod L
     if M % L == 0:
       y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_POS, aux=pos, aux_rows=L, **kw)
-      close(y, pre + pos.double().repeat(M // L, 1), 1e-4, 2e-3, "pos")
+      B.check_gemm(y, pre + pos.double().repeat(M // L, 1), x, wt, legacy=(1e-4, 2e-3), name="pos", n_adds=2)
     # forward GELU: both outputs (h rounded to bf16, g = gelu of that rounded h)
     g = torch.empty((M, N), device=dev, dtype=BF16)
     h = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_GELU, out2=g, **kw)
-    close(h, pre, 1e-2, 1e-2, "gelu: h")
-    close(g, _gelu_tanh64(h.double()), 1e-2, 1e-2, "gelu: g")
+    B.check_gemm(h, pre, x, wt, legacy=(1e-2, 1e-2), name="gelu: h")
+    B.check_gelu_g(g, h, legacy=(1e-2, 1e-2), name="gelu: g")
     # forward GELU_GD: g and gelu'(pre) from the fp32 pre-activation
     g4 = torch.empty((M, N), device=dev, dtype=BF16)
     d4 = torch.empty((M, N), device=dev, dtype=BF16)
     ops.gemm(x, w, bias=b, out=g4, epilogue=ops.EPI_GELU_GD, out2=d4, **kw)
     close(g4, _gelu_tanh64(pre), 1e-2, 1e-2, "gelu_gd: g")
     close(d4, _dgelu_tanh64(pre), 1e-2, 1e-2, "gelu_gd: g'")
+    B.check_gelu_g(g4, h, legacy=(1e-2, 1e-2), name="gelu_gd: g (of bf16(pre))")
+    B.check_gelu_dg(d4, h, legacy=(1e-2, 1e-2), name="gelu_gd: g' (of bf16(pre))")
     # backward GELU' x aux (+ emitted gelu, + fused column sums = the Dense_0 bias gradient)
     ref_bwd = acc * _dgelu_tanh64(hh.double())
     csref = ref_bwd.sum(0)
@@ -363,8 +370,8 @@ def test_fused_epilogues_multi_tile_vs_fp64(dev, fast, M, N, K, reserve):
     cs = torch.ones((N,), device=dev, dtype=F32)
     g2 = torch.empty((M, N), device=dev, dtype=BF16)
     o = ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_GELU_BWD_EMIT, aux=hh, out2=g2, colsum=cs, **kw)
-    close(o, ref_bwd, 1e-2, 2e-2, "gelu' emit: dX")
-    close(g2, _gelu_tanh64(hh.double()), 1e-2, 1e-2, "gelu' emit: g")
+    B.check_gelu_bwd(o, x, wt, hh, legacy=(1e-2, 2e-2), name="gelu' emit: dX", legacy_ref=ref_bwd)
+    B.check_gelu_g(g2, hh, legacy=(1e-2, 1e-2), name="gelu' emit: g")
     close(cs, 1.0 + csref, 1e-3, cstol, "gelu' emit: column sums")
     assert _rel_l2(cs - 1.0, csref) < 5e-3, "gelu' emit: column sums rel-L2"
     cs = torch.zeros((N,), device=dev, dtype=F32)
@@ -380,7 +387,7 @@ def test_fused_epilogues_multi_tile_vs_fp64(dev, fast, M, N, K, reserve):
     ref_mul = acc * dd.double()
     cs = torch.zeros((N,), device=dev, dtype=F32)
     o5 = ops.gemm(x, w, out_dtype=BF16, epilogue=ops.EPI_MUL, aux=dd, colsum=cs, **kw)
-    close(o5, ref_mul, 1e-2, 2e-2, "mul: dX")
+    B.check_mul(o5, x, wt, dd, legacy=(1e-2, 2e-2), name="mul: dX")
     close(cs, ref_mul.sum(0), 1e-3, 2e-3 * ref_mul.abs().sum(0).max().item(), "mul: column sums")
     assert _rel_l2(cs, ref_mul.sum(0)) < 5e-3, "mul: column sums rel-L2"
   finally:

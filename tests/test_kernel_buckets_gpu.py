@@ -25,6 +25,8 @@ import math
 import pytest
 import torch
 
+import _bounds as B
+
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -74,8 +76,7 @@ def _attn_check(dev, n, L, H, Dh, masked, cfg=None, seed=0):
     dqkv = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, kv_len=kv_len)
     dqkv_b = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, kv_len=kv_len, dbias=db)
     dqkv2 = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, kv_len=kv_len)
-  assert_close(lse, lse_ref, 1e-4, 1e-3, "lse")
-  assert_close(o, o_ref, 2e-2, 2e-2, "attn out")
+  B.check_attn_fwd(o, lse, qkv, n, L, H, Dh, lens, legacy_o=(2e-2, 2e-2), legacy_lse=(1e-4, 1e-3))
   assert_close(dqkv, g, 3e-2, 3e-2 * g.abs().max().item(), "dqkv")
   assert_close(db, 0.5 + g.sum(0), 2e-2, 2e-2 * g.abs().sum(0).max().item(), "fused qkv bias grad")
   assert torch.equal(o, o2) and torch.equal(lse, lse2), "forward: run-to-run difference"
@@ -217,8 +218,8 @@ def test_layernorm_f32_bucket(dev, D, rows):
   scale = 1 + 0.1 * rnd((D,), dev, 2); bias = 0.1 * rnd((D,), dev, 3)
   xr, sr, br, ref = _ln_ref(x, scale, bias, D)
   y_bf, y_f, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=rows, D=D, want_f32=True)
-  assert_close(y_f, ref, 1e-5, 1e-5, "ln fwd f32")
-  assert_close(y_bf, ref, 1e-2, 1e-2, "ln fwd bf16")
+  B.check_ln_fwd(y_f, x, scale, bias, legacy=(1e-5, 1e-5), name="ln fwd f32")
+  B.check_ln_fwd(y_bf, x, scale, bias, legacy=(1e-2, 1e-2), name="ln fwd bf16")
   y_bf2, y_f2, mean2, rstd2 = ops.layernorm_fwd(x, scale, bias, rows=rows, D=D, want_f32=True)
   assert torch.equal(y_f, y_f2) and torch.equal(y_bf, y_bf2) and torch.equal(rstd, rstd2)
   dy32 = rnd((rows, D), dev, 4)
@@ -233,8 +234,8 @@ def test_layernorm_f32_bucket(dev, D, rows):
       dx = ops.layernorm_bwd(dy, x, scale, mean, rstd, rows=rows, D=D, dres=dres, dx_bf16=dx_bf, dscale=dscale,
                              dbias=dbias, dx_colsum=dxsum)
       tag = f"(dy {dy.dtype}, dres {with_res})"
-      assert_close(dx, want, 1e-4, 1e-4, f"ln dx {tag}")
-      assert_close(dx_bf, want, 1e-2, 1e-2, f"ln dx bf16 {tag}")
+      B.check_ln_bwd(dx, x, scale, dy, dres=dres, legacy=(1e-4, 1e-4), name=f"ln dx {tag}")
+      B.check_ln_bwd(dx_bf, x, scale, dy, dres=dres, legacy=(1e-2, 1e-2), name=f"ln dx bf16 {tag}")
       assert_close(dxsum, 1.0 + dx.double().sum(0), 1e-4, 1e-3, f"ln dx colsum {tag}")
       assert_close(dscale, sr.grad, 1e-4, 1e-3, f"ln dscale {tag}")
       assert_close(dbias, br.grad, 1e-4, 1e-3, f"ln dbias {tag}")
@@ -249,8 +250,7 @@ def test_layernorm_f32_bucket(dev, D, rows):
     _, y, m_s, r_s = ops.layernorm_fwd(x, scale, bias, rows=n, D=D, row_stride=L, row_offset=1, want_bf16=False,
                                        want_f32=True)
     sel = x[:n * L].view(n, L, D)[:, 1].double()
-    assert_close(y, torch.nn.functional.layer_norm(sel, (D,), scale.double(), bias.double(), eps=1e-6), 1e-5, 1e-5,
-                 "strided ln fwd")
+    B.check_ln_fwd(y, sel, scale, bias, legacy=(1e-5, 1e-5), name="strided ln fwd")
     dys = rnd((n, D), dev, 6)
     xs = x[:n * L].contiguous()
     dxs = ops.layernorm_bwd(dys, xs, scale, m_s, r_s, rows=n, D=D, row_stride=L, row_offset=1)
@@ -258,6 +258,12 @@ def test_layernorm_f32_bucket(dev, D, rows):
     torch.nn.functional.layer_norm(xq.view(n, L, D)[:, 1], (D,), scale.double(), bias.double(),
                                    eps=1e-6).backward(dys.double())
     assert_close(dxs, xq.grad, 1e-4, 1e-4, "strided ln bwd: other rows stay 0")
+    B.check_ln_bwd(dxs.view(n, L, D)[:, 1], sel, scale, dys, legacy=(1e-4, 1e-4), name="strided ln bwd")
+  # rows of std 1e-2 / 1e-3 (pin eps) and |mean| / std = 4 in launches of their own without the fused column sums
+  # (rows 1, 4, 7, 10 feed the strided launch; rows = 1 runs each kind as row 0)
+  for dres in (None, rnd((rows, D), dev, 5)):
+    B.check_ln_edge_launch(ops, x, scale, bias, (dy32, dy32.to(BF16)), dres=dres,
+                           strided=(rows // 3, 3, 1) if rows > 1 and dres is None else None)
 
 
 def _bfx2(D):
@@ -280,8 +286,8 @@ def test_layernorm_bf16_stream_bucket(dev, D, rows):
   scale = 1 + 0.1 * rnd((D,), dev, 2); bias = 0.1 * rnd((D,), dev, 3)
   xr, sr, br, ref = _ln_ref(x, scale, bias, D)
   y_bf, y_f, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=rows, D=D, want_f32=True)
-  assert_close(y_f, ref, 1e-5, 1e-5, "ln fwd f32 (bf16 x)")
-  assert_close(y_bf, ref, 1e-2, 1e-2, "ln fwd bf16 (bf16 x)")
+  B.check_ln_fwd(y_f, x, scale, bias, legacy=(1e-5, 1e-5), name="ln fwd f32 (bf16 x)")
+  B.check_ln_fwd(y_bf, x, scale, bias, legacy=(1e-2, 1e-2), name="ln fwd bf16 (bf16 x)")
   dy32 = rnd((rows, D), dev, 4)
   for dy in (dy32.to(BF16), dy32):
     xr.grad = sr.grad = br.grad = None
@@ -294,12 +300,15 @@ def test_layernorm_bf16_stream_bucket(dev, D, rows):
                              dx_colsum=dxsum)
       tag = f"(dy {dy.dtype}, dres {with_res})"
       assert dx.dtype == BF16
-      assert_close(dx, want, 1e-2, 1e-2, f"ln dx (bf16 stream) {tag}")
+      B.check_ln_bwd(dx, x, scale, dy, dres=dres, legacy=(1e-2, 1e-2), name=f"ln dx (bf16 stream) {tag}")
       assert_close(dxsum, 1.0 + want.sum(0), 1e-4, 1e-3, f"ln dx colsum {tag}")
       assert_close(dscale, sr.grad, 1e-4, 1e-3, f"ln dscale {tag}")
       assert_close(dbias, br.grad, 1e-4, 1e-3, f"ln dbias {tag}")
       dx2 = ops.layernorm_bwd(dy, x, scale, mean, rstd, rows=rows, D=D, dres=dres)
       assert torch.equal(dx, dx2), f"run-to-run / colsum-variant difference {tag}"
+  # the edge rows in launches of their own without the fused column sums (rows = 1: each kind as row 0)
+  for dres in (None, rnd((rows, D), dev, 5).to(BF16)):
+    B.check_ln_edge_launch(ops, x, scale, bias, (dy32.to(BF16), dy32), dres=dres)
 
 
 # ------------------------------------------------------------------ GEMM ----
@@ -316,10 +325,10 @@ def test_gemm_general_fourth_layout(dev, M, N, K):
   for bb in (None, bias):
     ref = prod + (bb.double() if bb is not None else 0)
     y = ops.gemm(a, b, bias=bb, out_dtype=F32, **kw)
-    assert_close(y, ref, 1e-4, 1e-3, "gemm<0,1> f32")
+    B.check_gemm(y, ref, a.T, b.T, legacy=(1e-4, 1e-3), name="gemm<0,1> f32")
     assert torch.equal(y, ops.gemm(a, b, bias=bb, out_dtype=F32, **kw))
     y16 = ops.gemm(a, b, bias=bb, out_dtype=BF16, **kw)
-    assert_close(y16, ref, 1e-2, 1e-2, "gemm<0,1> bf16")
+    B.check_gemm(y16, ref, a.T, b.T, legacy=(1e-2, 1e-2), name="gemm<0,1> bf16")
 
 
 @pytest.mark.parametrize("epi", ["none", "gelu"])
@@ -332,7 +341,7 @@ def test_rolling_epilogue_bit8(dev, epi):
   w = rnd((N, K), dev, 22, 0.05, dtype=BF16)
   b = rnd((N,), dev, 23)
   kw = dict(a_kmajor=True, b_kmajor=True)
-  pre = a.float() @ w.float().T + b
+  pre = a.double() @ w.double().T + b.double()
 
   def run():
     if epi == "none":
@@ -350,11 +359,13 @@ def test_rolling_epilogue_bit8(dev, epi):
     for x, y in zip(r, ref):
       assert torch.equal(x, y), f"gemm_roll bit 8 ({epi}) differs from the full-epilogue kernel"
   if epi == "none":
-    assert_close(new[0][0], pre, 1e-2, 1e-2, "roll8 bias bf16")
-    assert_close(new[0][1], 0.5 * (pre - b), 1e-2, 1e-2, "roll8 alpha bf16")
+    B.check_gemm(new[0][0], pre, a, w.T, legacy=(1e-2, 1e-2), name="roll8 bias bf16")
+    B.check_gemm(new[0][1], 0.5 * (pre - b.double()), a, w.T, legacy=(1e-2, 1e-2), name="roll8 alpha bf16", n_adds=0,
+                 alpha=0.5)
   else:
-    assert_close(new[0][0], pre, 1e-2, 1e-2, "roll8 gelu pre")
-    assert_close(new[0][1], torch.nn.functional.gelu(pre, approximate="tanh"), 1e-2, 1e-2, "roll8 gelu out")
+    B.check_gemm(new[0][0], pre, a, w.T, legacy=(1e-2, 1e-2), name="roll8 gelu pre")
+    assert_close(new[0][1], B.gelu_tanh64(pre), 1e-2, 1e-2, "roll8 gelu out")
+    B.check_gelu_g(new[0][1], new[0][0], legacy=(1e-2, 1e-2), name="roll8 gelu out (of the stored h)")
 
 
 # M or N = 256 k +- 8 and K = 64 k +- 8: only (512, 768, 128) and its dW transpose qualify for the 256 x 256 path
@@ -372,7 +383,7 @@ def test_gemm_fast_path_edges(dev, M, N, K, fast):
   a = rnd((M, K), dev, 31, dtype=BF16)
   w = rnd((N, K), dev, 32, 0.05, dtype=BF16)
   bias = rnd((N,), dev, 33)
-  ref = a.float() @ w.float().T + bias
+  ref = a.double() @ w.double().T + bias.double()
   with ops.option("fast_path", 1):
     c0 = ops.ctx_get("gemm256_calls")
     outs = [ops.gemm(a, w, a_kmajor=True, b_kmajor=True, bias=bias, out_dtype=F32) for _ in range(3)]
@@ -386,11 +397,12 @@ def test_gemm_fast_path_edges(dev, M, N, K, fast):
     ops.gemm(x, dy, a_kmajor=False, b_kmajor=False, out=dw, epilogue=ops.EPI_ATOMIC)
     assert (ops.ctx_get("gemm256_calls") > c1) == fast, "fast-path selection (dW layout)"
   close_ref = dict(rtol=1e-4, atol=2e-3)
-  assert_close(outs[0], ref, close_ref["rtol"], close_ref["atol"], "f32")
+  B.check_gemm(outs[0], ref, a, w.T, legacy=(close_ref["rtol"], close_ref["atol"]), name="f32")
   for o in outs[1:]:
     assert torch.equal(o, outs[0]), "run-to-run difference"
-  assert_close(o16, ref, 1e-2, 1e-2, "bf16")
-  assert_close(dw, base.double() + x.double().T @ dy.double(), 1e-4, 1e-4 * K ** 0.5 * 4, "dW")
+  B.check_gemm(o16, ref, a, w.T, legacy=(1e-2, 1e-2), name="bf16")
+  B.check_gemm(dw, base.double() + x.double().T @ dy.double(), x.T, dy, legacy=(1e-4, 1e-4 * K ** 0.5 * 4), name="dW",
+               n_adds=2 + 8)
   if fast:
     with ops.option("fast_path", 0):
       gen = ops.gemm(a, w, a_kmajor=True, b_kmajor=True, bias=bias, out_dtype=F32)

@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+import _bounds as B
+
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -38,11 +40,11 @@ def test_gemm_forward_layout(dev, M, N, K):
   x = rnd((M, K), dev, 0, dtype=BF16)
   w = rnd((K, N), dev, 1, 0.05, dtype=BF16)   # asymmetric: catches transposes
   b = rnd((N,), dev, 2)
-  ref = x.float() @ w.float() + b
+  ref = x.double() @ w.double() + b.double()
   y = ops.gemm(x, w, a_kmajor=True, b_kmajor=False, bias=b, out_dtype=F32)
-  assert_close(y, ref, 1e-4, 1e-3, "gemm f32")
+  B.check_gemm(y, ref, x, w, legacy=(1e-4, 1e-3), name="gemm f32")
   y16 = ops.gemm(x, w, a_kmajor=True, b_kmajor=False, bias=b, out_dtype=BF16)
-  assert_close(y16, ref, 1e-2, 1e-2, "gemm bf16")
+  B.check_gemm(y16, ref, x, w, legacy=(1e-2, 1e-2), name="gemm bf16")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 128, 256), (1568, 768, 3072), (77, 64, 128)])
@@ -51,9 +53,9 @@ def test_gemm_dx_layout(dev, M, N, K):
   from big_vision_amd import ops
   dy = rnd((M, K), dev, 3, dtype=BF16)
   w = rnd((N, K), dev, 4, 0.05, dtype=BF16)
-  ref = dy.float() @ w.float().T
+  ref = dy.double() @ w.double().T
   dx = ops.gemm(dy, w, a_kmajor=True, b_kmajor=True, out_dtype=BF16)
-  assert_close(dx, ref, 1e-2, 1e-2, "gemm dx")
+  B.check_gemm(dx, ref, dy, w.T, legacy=(1e-2, 1e-2), name="gemm dx", n_adds=0)
 
 
 @pytest.mark.parametrize("T,Din,Dout,split", [(512, 128, 256, 0), (1568, 768, 2304, 0), (333, 64, 72, 3), (64, 8, 8, 1)])
@@ -63,10 +65,11 @@ def test_gemm_dw_layout(dev, T, Din, Dout, split):
   x = rnd((T, Din), dev, 5, dtype=BF16)
   dy = rnd((T, Dout), dev, 6, dtype=BF16)
   base = rnd((Din, Dout), dev, 7)
-  ref = base + x.float().T @ dy.float()
+  ref = base.double() + x.double().T @ dy.double()
   out = base.clone()
   ops.gemm(x, dy, a_kmajor=False, b_kmajor=False, out=out, epilogue=ops.EPI_ATOMIC, split_k=split)
-  assert_close(out, ref, 1e-4, 1e-4 * math.sqrt(T) * 4, "gemm dw")
+  # fp32 atomics: the base and every split-K partial are one more fp32 add each
+  B.check_gemm(out, ref, x.T, dy, legacy=(1e-4, 1e-4 * math.sqrt(T) * 4), name="gemm dw", n_adds=2 + max(split, 1))
 
 
 def test_gemm_epilogues(dev):
@@ -75,20 +78,22 @@ def test_gemm_epilogues(dev):
   x = rnd((M, K), dev, 8, dtype=BF16)
   w = rnd((K, N), dev, 9, 0.1, dtype=BF16)
   b = rnd((N,), dev, 10)
-  pre = x.float() @ w.float() + b
+  pre = x.double() @ w.double() + b.double()
   res = rnd((M, N), dev, 11)
   y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=res)
-  assert_close(y, pre + res, 1e-4, 1e-3, "residual")
+  B.check_gemm(y, pre + res.double(), x, w, legacy=(1e-4, 1e-3), name="residual", n_adds=2)
   resb = res.to(BF16)   # bf16 residual stream: aux and C bf16
   yb = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_RESIDUAL, aux=resb)
-  assert_close(yb, pre + resb.float(), 1e-2, 1e-2, "residual (bf16 stream)")
+  B.check_gemm(yb, pre + resb.double(), x, w, legacy=(1e-2, 1e-2), name="residual (bf16 stream)", n_adds=2)
   pos = rnd((L, N), dev, 12)
   y = ops.gemm(x, w, bias=b, out_dtype=F32, epilogue=ops.EPI_POS, aux=pos, aux_rows=L)
-  assert_close(y, pre + pos.repeat(M // L, 1), 1e-4, 1e-3, "pos")
+  B.check_gemm(y, pre + pos.double().repeat(M // L, 1), x, w, legacy=(1e-4, 1e-3), name="pos", n_adds=2)
   g = torch.empty((M, N), device=dev, dtype=BF16)
   h = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_GELU, out2=g)
-  assert_close(h, pre, 1e-2, 1e-2, "gelu pre")
-  assert_close(g, torch.nn.functional.gelu(pre, approximate="tanh"), 1e-2, 1e-2, "gelu out")
+  B.check_gemm(h, pre, x, w, legacy=(1e-2, 1e-2), name="gelu pre")
+  # g = gelu of the bf16 h the kernel stored (bv_common.h), checked stage by stage (the check against gelu(pre) stays)
+  assert_close(g, B.gelu_tanh64(pre), 1e-2, 1e-2, "gelu out")
+  B.check_gelu_g(g, h, legacy=(1e-2, 1e-2), name="gelu out (of the stored h)")
   # the single-output epilogue of a forward that saves no context writes the same activation bits and nothing else
   g1 = ops.gemm(x, w, bias=b, out_dtype=BF16, epilogue=ops.EPI_GELU_G)
   assert torch.equal(g1, g), "BV_EPI_GELU_G differs from the activation BV_EPI_GELU writes"
@@ -96,17 +101,15 @@ def test_gemm_epilogues(dev):
   dg_in = rnd((M, K), dev, 13, dtype=BF16)
   w2 = rnd((N, K), dev, 14, 0.1, dtype=BF16)
   hh = rnd((M, N), dev, 15, dtype=BF16)
-  hf = hh.float().requires_grad_(True)
-  torch.nn.functional.gelu(hf, approximate="tanh").sum().backward()
-  ref = (dg_in.float() @ w2.float().T) * hf.grad
+  ref = (dg_in.double() @ w2.double().T) * B.dgelu_tanh64(hh)
   out = ops.gemm(dg_in, w2, a_kmajor=True, b_kmajor=True, out_dtype=BF16,
                  epilogue=ops.EPI_GELU_BWD, aux=hh)
-  assert_close(out, ref, 1e-2, 2e-2, "gelu bwd")
+  B.check_gelu_bwd(out, dg_in, w2.T, hh, legacy=(1e-2, 2e-2), name="gelu bwd")
   g2 = torch.empty((M, N), device=dev, dtype=BF16)
   out2 = ops.gemm(dg_in, w2, a_kmajor=True, b_kmajor=True, out_dtype=BF16,
                   epilogue=ops.EPI_GELU_BWD_EMIT, aux=hh, out2=g2)
-  assert_close(out2, ref, 1e-2, 2e-2, "gelu bwd (emit)")
-  assert_close(g2, torch.nn.functional.gelu(hh.float(), approximate="tanh"), 1e-2, 1e-2, "emitted gelu")
+  B.check_gelu_bwd(out2, dg_in, w2.T, hh, legacy=(1e-2, 2e-2), name="gelu bwd (emit)")
+  B.check_gelu_g(g2, hh, legacy=(1e-2, 1e-2), name="emitted gelu")
   g3 = torch.empty((M, N), device=dev, dtype=BF16)
   ops.gemm(dg_in, w2, a_kmajor=True, b_kmajor=True, out_dtype=BF16, epilogue=ops.EPI_GELU_BWD_EMIT, aux=h, out2=g3)
   assert torch.equal(g3, g), "gelu(h) re-emitted by the backward differs from the forward's"
@@ -176,8 +179,8 @@ def test_layernorm(dev, rows, D):
   br = bias.double().requires_grad_(True)
   ref = torch.nn.functional.layer_norm(xr, (D,), sr, br, eps=1e-6)
   y_bf, y_f, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=rows, D=D, want_f32=True)
-  assert_close(y_f, ref, 1e-5, 1e-5, "ln fwd f32")
-  assert_close(y_bf, ref, 1e-2, 1e-2, "ln fwd bf16")
+  B.check_ln_fwd(y_f, x, scale, bias, legacy=(1e-5, 1e-5), name="ln fwd f32")
+  B.check_ln_fwd(y_bf, x, scale, bias, legacy=(1e-2, 1e-2), name="ln fwd bf16")
   dy = rnd((rows, D), dev, 4)
   dres = rnd((rows, D), dev, 5)
   ref.backward(dy.double())
@@ -186,9 +189,9 @@ def test_layernorm(dev, rows, D):
   dxsum = torch.ones(D, device=dev)          # accumulated (+=) into
   dx = ops.layernorm_bwd(dy, x, scale, mean, rstd, rows=rows, D=D, dres=dres, dx_bf16=dx_bf,
                          dscale=dscale, dbias=dbias, dx_colsum=dxsum)
-  assert_close(dx, xr.grad + dres.double(), 1e-4, 1e-4, "ln dx")
+  B.check_ln_bwd(dx, x, scale, dy, dres=dres, legacy=(1e-4, 1e-4), name="ln dx")
   assert_close(dxsum, 1.0 + dx.double().sum(0), 1e-4, 1e-3, "ln dx colsum (fused bias grad)")
-  assert_close(dx_bf, xr.grad + dres.double(), 1e-2, 1e-2, "ln dx bf16")
+  B.check_ln_bwd(dx_bf, x, scale, dy, dres=dres, legacy=(1e-2, 1e-2), name="ln dx bf16")
   assert_close(dscale, sr.grad, 1e-4, 1e-3, "ln dscale")
   assert_close(dbias, br.grad, 1e-4, 1e-3, "ln dbias")
   # bv_layernorm_bwd_y: the same backward that also re-emits the forward's bf16 output (light contexts):
@@ -203,7 +206,10 @@ def test_layernorm(dev, rows, D):
   dx2 = ops.layernorm_bwd(dyb, x, scale, mean, rstd, rows=rows, D=D)
   xr.grad = None
   torch.nn.functional.layer_norm(xr, (D,), sr, br, eps=1e-6).backward(dyb.double())
-  assert_close(dx2, xr.grad, 1e-4, 1e-4, "ln dx (bf16 dy)")
+  B.check_ln_bwd(dx2, x, scale, dyb, legacy=(1e-4, 1e-4), name="ln dx (bf16 dy)")
+  # rows of std 1e-2 / 1e-3 (pin eps) and |mean| / std = 4 (fast-variance cancellation), in launches of their own
+  # that fuse no column sums (_bounds.check_ln_edge_launch)
+  B.check_ln_edge_launch(ops, x, scale, bias, (dy, dyb), dres=dres)
 
 
 @pytest.mark.parametrize("rows,D", [(1568, 768), (37, 128), (64, 1024), (9, 384), (5, 1152), (3, 2048)])
@@ -217,8 +223,8 @@ def test_layernorm_bf16_stream(dev, rows, D):
   br = bias.double().requires_grad_(True)
   ref = torch.nn.functional.layer_norm(xr, (D,), sr, br, eps=1e-6)
   y_bf, y_f, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=rows, D=D, want_f32=True)
-  assert_close(y_f, ref, 1e-5, 1e-5, "ln fwd f32 (bf16 x)")
-  assert_close(y_bf, ref, 1e-2, 1e-2, "ln fwd bf16 (bf16 x)")
+  B.check_ln_fwd(y_f, x, scale, bias, legacy=(1e-5, 1e-5), name="ln fwd f32 (bf16 x)")
+  B.check_ln_fwd(y_bf, x, scale, bias, legacy=(1e-2, 1e-2), name="ln fwd bf16 (bf16 x)")
   assert_close(mean, xr.mean(-1), 1e-5, 1e-5, "mean")
   for dy in (rnd((rows, D), dev, 4), rnd((rows, D), dev, 4).to(BF16)):
     dres = rnd((rows, D), dev, 5).to(BF16)
@@ -230,7 +236,7 @@ def test_layernorm_bf16_stream(dev, rows, D):
                            dx_colsum=dxsum)
     assert dx.dtype == BF16
     want = xr.grad + dres.double()
-    assert_close(dx, want, 1e-2, 1e-2, "ln dx (bf16 stream)")
+    B.check_ln_bwd(dx, x, scale, dy, dres=dres, legacy=(1e-2, 1e-2), name="ln dx (bf16 stream)")
     assert_close(dxsum, 1.0 + want.sum(0), 1e-4, 1e-3, "ln dx colsum is summed in fp32, before the rounding")
     assert_close(dscale, sr.grad, 1e-4, 1e-3, "ln dscale")
     assert_close(dbias, br.grad, 1e-4, 1e-3, "ln dbias")
@@ -240,13 +246,17 @@ def test_layernorm_bf16_stream(dev, rows, D):
     _, y, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=n, D=D, row_stride=L, row_offset=L - 1,
                                          want_bf16=False, want_f32=True)
     sel = x[:n * L].view(n, L, D)[:, -1].double()
-    assert_close(y, torch.nn.functional.layer_norm(sel, (D,), scale.double(), bias.double(), eps=1e-6), 1e-5, 1e-5,
-                 "strided ln (bf16 x)")
+    B.check_ln_fwd(y, sel, scale, bias, legacy=(1e-5, 1e-5), name="strided ln (bf16 x)")
     dy = rnd((n, D), dev, 6)
     dxs = ops.layernorm_bwd(dy, x[:n * L].contiguous(), scale, mean, rstd, rows=n, D=D, row_stride=L, row_offset=L - 1)
     xq = x[:n * L].double().requires_grad_(True)
     torch.nn.functional.layer_norm(xq.view(n, L, D)[:, -1], (D,), scale.double(), bias.double(), eps=1e-6).backward(dy.double())
     assert_close(dxs, xq.grad, 1e-2, 1e-2, "strided ln bwd (bf16 stream): other rows stay 0")
+    B.check_ln_bwd(dxs.view(n, L, D)[:, -1], sel, scale, dy, legacy=(1e-2, 1e-2), name="strided ln bwd (bf16 stream)")
+  # the edge rows, including the rows the strided launch selects, in launches without fused column sums
+  dy32 = rnd((rows, D), dev, 4)
+  B.check_ln_edge_launch(ops, x, scale, bias, (dy32, dy32.to(BF16)), dres=rnd((rows, D), dev, 5).to(BF16),
+                         strided=(n, L, L - 1), idx=sorted(set(B.LN_EDGE_IDX) | {L - 1, 2 * L - 1, 3 * L - 1}))
 
 
 def test_cast_f32(dev):
@@ -265,7 +275,7 @@ def test_layernorm_strided_rows(dev):
   _, y, mean, rstd = ops.layernorm_fwd(x, scale, bias, rows=n, D=D, row_stride=L, row_offset=L - 1,
                                        want_bf16=False, want_f32=True)
   sel = x.view(n, L, D)[:, -1]
-  assert_close(y, torch.nn.functional.layer_norm(sel, (D,), scale, bias, eps=1e-6), 1e-5, 1e-5, "strided ln")
+  B.check_ln_fwd(y, sel, scale, bias, legacy=(1e-5, 1e-5), name="strided ln")
   dy = rnd((n, D), dev, 4)
   dxsum = torch.zeros(D, device=dev)
   dx = ops.layernorm_bwd(dy, x, scale, mean, rstd, rows=n, D=D, row_stride=L, row_offset=L - 1,
@@ -274,6 +284,10 @@ def test_layernorm_strided_rows(dev):
   xr = x.clone().requires_grad_(True)
   torch.nn.functional.layer_norm(xr.view(n, L, D)[:, -1], (D,), scale, bias, eps=1e-6).backward(dy)
   assert_close(dx, xr.grad, 1e-4, 1e-5, "strided ln bwd")
+  B.check_ln_bwd(dx.view(n, L, D)[:, -1], sel, scale, dy, legacy=(1e-4, 1e-5), name="strided ln bwd")
+  # all six selected rows as edge rows, in launches without the fused column sums
+  B.check_ln_edge_launch(ops, x, scale, bias, (rnd((n * L, D), dev, 4),), strided=(n, L, L - 1),
+                         idx=[L - 1 + i * L for i in range(n)])
 
 
 # ------------------------------------------------------------- Attention -----
@@ -309,8 +323,7 @@ def test_attention_key_padding_mask(dev, n, L, H):
   p = torch.softmax(s, -1)
   o_ref = torch.einsum("nhqk,nkhd->nqhd", p, v).reshape(n * L, H * 64)
   o, lse = ops.attn_fwd(qkv, n, L, H, kv_len=kv_len)
-  assert_close(lse, torch.logsumexp(s, -1), 1e-4, 1e-3, "masked lse")
-  assert_close(o, o_ref, 2e-2, 2e-2, "masked attn out")
+  B.check_attn_fwd(o, lse, qkv, n, L, H, 64, lens, legacy_o=(2e-2, 2e-2), legacy_lse=(1e-4, 1e-3), name="masked attn")
   d_o = rnd((n * L, H * 64), dev, 6, dtype=BF16)
   o_ref.backward(d_o.double())
   db = torch.zeros((3 * H * 64,), device=dev)
@@ -359,8 +372,7 @@ def _attention_case(dev, n, L, H):
   qr = qkv.double().requires_grad_(True)
   o_ref, lse_ref = _attn_ref(qr, n, L, H)
   o, lse = ops.attn_fwd(qkv, n, L, H)
-  assert_close(lse, lse_ref, 1e-4, 1e-3, "lse")
-  assert_close(o, o_ref, 2e-2, 2e-2, "attn out")
+  B.check_attn_fwd(o, lse, qkv, n, L, H, 64, legacy_o=(2e-2, 2e-2), legacy_lse=(1e-4, 1e-3))
   d_o = rnd((n * L, H * 64), dev, 2, dtype=BF16)
   o_ref.backward(d_o.double())
   dqkv = ops.attn_bwd(qkv, o, d_o, lse, n, L, H)
@@ -461,8 +473,7 @@ def test_attention_peaked_softmax(dev):
   o_ref, lse_ref = _attn_ref(qkv, n, L, H)
   o, lse = ops.attn_fwd(qkv, n, L, H)
   assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all()
-  assert_close(lse, lse_ref, 1e-3, 1e-2, "lse peaked")
-  assert_close(o, o_ref, 3e-2, 3e-2, "attn out peaked")
+  B.check_attn_fwd(o, lse, qkv, n, L, H, 64, legacy_o=(3e-2, 3e-2), legacy_lse=(1e-3, 1e-2), name="attn peaked")
 
 
 @pytest.mark.parametrize("n,L,H", [(4, 196, 2), (3, 16, 1), (5, 70, 3)])
@@ -506,8 +517,7 @@ def test_attention_other_head_dims(dev, n, L, H, Dh, masked):
   o_ref = torch.einsum("nhqk,nkhd->nqhd", p, v).reshape(n * L, H * Dh)
   o, lse = ops.attn_fwd(qkv, n, L, H, kv_len=kv_len)
   assert o.shape == (n * L, H * Dh)
-  assert_close(lse, torch.logsumexp(s, -1), 1e-4, 1e-3, "lse")
-  assert_close(o, o_ref, 2e-2, 2e-2, "attn out")
+  B.check_attn_fwd(o, lse, qkv, n, L, H, Dh, lens if masked else None, legacy_o=(2e-2, 2e-2), legacy_lse=(1e-4, 1e-3))
   d_o = rnd((n * L, H * Dh), dev, 12, dtype=BF16)
   o_ref.backward(d_o.double())
   db = torch.full((3 * H * Dh,), 0.25, device=dev)
@@ -668,6 +678,67 @@ def test_siglip_loss_kernel_vs_oracle(dev, n, B, off, t0, b0):
   dzt = t * raw.double().cpu().T @ zid.detach()
   assert_close(dzi, zid.grad, 1e-4, 1e-7, "dzimg")
   assert_close(dzt, ztd.grad, 1e-4, 1e-7, "dztxt")
+
+
+def test_siglip_loss_kernel_extreme_logits(dev):
+  """t = 100 (t' is not clipped) and b = -10: logits from about -110 to +90, where exp(-m s) of the naive
+  log(1 + exp(.)) overflows fp32; loss, dt', db and G vs fp64."""
+  import bv_oracle as O
+  from big_vision_amd import ops
+  zi, zt = B.siglip_extreme_inputs(dev)
+  n, Bn, off = zi.shape[0], zt.shape[0], 14
+  tp = torch.tensor([math.log(100.0)], device=dev); bp = torch.tensor([-10.0], device=dev)
+  raw = torch.zeros((n, Bn), device=dev)
+  ops.sgemm(zi, zi.shape[1], 1, zt, 1, zt.shape[1], raw, n, Bn, zi.shape[1])
+  rawd = raw.double().cpu()
+  tpd = tp.double().cpu().requires_grad_(True); bpd = bp.double().cpu().requires_grad_(True)
+  logits = rawd * torch.exp(tpd) + bpd
+  assert logits.max().item() > 88.8 and logits.min().item() < -100
+  m = -torch.ones_like(logits); m[torch.arange(n), off + torch.arange(n)] = 1.0
+  lg = logits.detach().requires_grad_(True)
+  loss_ref = (-O.log_sigmoid(m * lg).sum(-1)).sum() / Bn
+  loss_ref.backward()
+  (dt_ref,) = torch.autograd.grad(((-O.log_sigmoid(m * logits).sum(-1)).sum() / Bn), tpd, retain_graph=True)
+  (db_ref,) = torch.autograd.grad(((-O.log_sigmoid(m * logits).sum(-1)).sum() / Bn), bpd)
+  stats = torch.zeros(3, device=dev, dtype=torch.float64)
+  ops.siglip_loss_(raw, tp, bp, stats, off, Bn)
+  assert torch.isfinite(raw).all() and torch.isfinite(stats).all()
+  B.check(stats[0:1].cpu(), loss_ref.detach().reshape(1), None, legacy=(1e-5, 1e-6), name="siglip loss (t = 100)")
+  B.check(stats[1:2].cpu(), dt_ref.reshape(1), None, legacy=(1e-4, 1e-6), name="siglip dt' (t = 100)")
+  B.check(stats[2:3].cpu(), db_ref.reshape(1), None, legacy=(1e-4, 1e-6), name="siglip db (t = 100)")
+  B.check(raw.cpu(), lg.grad, None, legacy=(1e-4, 1e-7), name="siglip G = dL/dlogits (t = 100)")
+
+
+def test_softmax_xent_extreme_logits(dev):
+  """Logits up to +-1e3: the max subtraction keeps every exp finite; loss and dlogits vs fp64."""
+  import bv_oracle as O
+  from big_vision_amd import ops
+  logits, labels = B.softmax_xent_extreme_inputs(dev)
+  lr = logits.double().cpu().requires_grad_(True)
+  ref = O.softmax_xent(lr, labels.double().cpu())
+  ref.backward()
+  acc = torch.zeros(1, device=dev, dtype=torch.float64)
+  dl = ops.softmax_xent(logits, labels, acc)
+  B.check(acc.cpu(), ref.detach().reshape(1), None, legacy=(1e-5, 1e-6), name="xent (|logits| <= 1e3)")
+  B.check(dl.cpu(), lr.grad, None, legacy=(1e-4, 1e-7), name="dlogits (|logits| <= 1e3)")
+
+
+def test_sigmoid_xent_extreme_logits(dev):
+  """Logits beyond +-90 (exp overflows fp32 above 88.7) up to +-1e3; loss (with and without the gradient) and dlogits
+  vs fp64."""
+  import bv_oracle as O
+  from big_vision_amd import ops
+  logits, labels = B.sigmoid_xent_extreme_inputs(dev)
+  lr = logits.double().cpu().requires_grad_(True)
+  ref = O.sigmoid_xent(lr, labels.double().cpu())
+  ref.backward()
+  acc = torch.zeros(1, device=dev, dtype=torch.float64)
+  dl = ops.sigmoid_xent(logits, labels, acc)
+  B.check(acc.cpu(), ref.detach().reshape(1), None, legacy=(1e-5, 1e-5), name="sigmoid xent (|logits| > 90)")
+  B.check(dl.cpu(), lr.grad, None, legacy=(1e-4, 1e-7), name="sigmoid dlogits (|logits| > 90)")
+  acc2 = torch.zeros(1, device=dev, dtype=torch.float64)
+  assert ops.sigmoid_xent(logits, labels, acc2, want_grad=False) is None
+  B.check(acc2.cpu(), ref.detach().reshape(1), None, legacy=(1e-5, 1e-5), name="sigmoid xent fwd-only (|logits| > 90)")
 
 
 def test_softmax_xent(dev):

@@ -1,0 +1,428 @@
+"""Proof, on the CPU, that the bounds of tests/_bounds.py bite: for every family of tightened GPU checks, the bound
+ACCEPTS an emulation of the prescribed arithmetic (fp32 / bf16 steps as the kernels promise them, on the GPU tests'
+own seeded inputs) and REJECTS every mutant of that family's catalogue - an emulation that makes one plausible slip.
+Each (family, mutant) prints one line with the number of elements rejected (pytest -s).
+
+Catalogue notes:
+  * "gelu' rounded to bf16 before the product" is not a slip here: it is the contract of the fused GELU' backward
+    (bv_common.h mlp_act_from_h, gemm256.hip: gelu' is rounded to bf16 as GELU_GD stores it, so every context kind
+    feeds the backward the same bits - test_gemm256_gpu.py asserts MUL(GELU_GD's d) == GELU_BWD bit for bit).  The
+    catalogue holds the opposite slip, an unrounded fp32 gelu', which the stage bound rejects.
+  * The attention backward (dqkv) and the column-sum / dW / loss outputs keep their previous tolerances: the model
+    does not justify a tighter bound for them (dqkv goes through bf16 P and dS operands, two contractions and the
+    delta subtraction).  Their mutants below are rejected by those tolerances.
+  * The attention P term is 2^-8 sum P|v|: one round-to-nearest-even of each bf16 P (8 significant bits, unit
+    roundoff 2^-8).  A 2^-9 term would reject the prescribed arithmetic itself (err / bound 1.04 on the inputs of
+    test_kernels_gpu.py::test_attention[2-64-3]).
+  No mutant of the catalogue is left unrejected.
+"""
+import math
+
+import pytest
+import torch
+
+import _bounds as B
+
+BF16, F32 = torch.bfloat16, torch.float32
+CPU = "cpu"
+ROWS = []
+
+
+def _rec(family, mutant, n, total):
+  ROWS.append((family, mutant, n, total))
+  print(f"[power] {family:10s} {mutant:58s} rejected {n:>7d} / {total}")
+
+
+def rne(x):
+  return x.float().to(BF16).float()
+
+
+def trunc(x):
+  return (x.float().contiguous().view(torch.int32) & ~0xFFFF).view(F32).to(BF16).float()
+
+
+def accept(family, name, out, ref, bound, legacy, lo_hi=None):
+  n = B.count_rejected(out, ref, bound, legacy, lo_hi)
+  _rec(family, "ACCEPT " + name, n, out.numel())
+  assert n == 0, f"{family}: the bound rejects the prescribed arithmetic ({name}) on {n} elements"
+
+
+def reject(family, name, out, ref, bound, legacy, lo_hi=None):
+  n = B.count_rejected(out, ref, bound, legacy, lo_hi)
+  _rec(family, name, n, out.numel())
+  assert n > 0, f"{family}: mutant '{name}' passes the bound"
+  return n
+
+
+# ------------------------------------------------------------------ GEMM ----
+def test_gemm_bounds_bite():
+  """Inputs of test_gemm256_gpu.py::test_nt_matches_reference at 512 x 768 x 768 (bias, bf16 and fp32 out) and of the
+  +residual epilogue on the fp32 stream."""
+  M, N, K = 512, 768, 768
+  a = B.rnd((M, K), CPU, 1, dtype=BF16)
+  w = B.rnd((N, K), CPU, 2, 0.05, dtype=BF16)
+  bias = B.rnd((N,), CPU, 3)
+  prod64 = a.double() @ w.double().T
+  ref = prod64 + bias.double()
+  ap = B.absprod(a, w.T)
+  bnd = B.gemm_bf16(ref, ap, K)
+  leg = (1e-2, 1e-2)
+  prod32 = a.float() @ w.float().T
+  pre32 = prod32 + bias
+  accept("gemm", "fp32 matmul + bias, RNE to bf16", rne(pre32), ref, bnd, leg)
+  reject("gemm", "truncate fp32 to bf16 (no RNE)", trunc(pre32), ref, bnd, leg)
+  reject("gemm", "+bias after rounding the product to bf16", rne(rne(prod32) + bias), ref, bnd, leg)
+  acc = torch.zeros(M, N)
+  for k0 in range(0, K, 64):
+    acc = rne(acc + a[:, k0:k0 + 64].float() @ w[:, k0:k0 + 64].float().T)
+  reject("gemm", "accumulator rounded to bf16 once per 64-wide K-tile", rne(acc + bias), ref, bnd, leg)
+  tile = a[:, 320:384].float() @ w[:, 320:384].float().T
+  reject("gemm", "one 64-wide K-tile dropped", rne(pre32 - tile), ref, bnd, leg)
+  reject("gemm", "one 64-wide K-tile repeated", rne(pre32 + tile), ref, bnd, leg)
+  o = rne(pre32)
+  m1 = o.clone(); m1[255::256] = o[254::256]
+  reject("gemm", "last row of each 256 tile taken from its neighbour", m1, ref, bnd, leg)
+  m2 = o.clone(); m2[:, 255::256] = o[:, 254::256]
+  reject("gemm", "last column of each 256 tile taken from its neighbour", m2, ref, bnd, leg)
+  # fp32 outputs: bias (legacy 1e-4 / 2e-3) and +residual on the fp32 stream
+  bf = B.gemm_f32(ref, ap, K)
+  accept("gemm", "fp32 out: fp32 matmul + bias", pre32, ref, bf, (1e-4, 2e-3))
+  reject("gemm", "fp32 out: one 64-wide K-tile dropped", pre32 - tile, ref, bf, (1e-4, 2e-3))
+  res = B.rnd((M, N), CPU, 11)
+  rref = ref + res.double()
+  br = B.gemm_f32(rref, ap, K, n_adds=2)
+  accept("gemm", "fp32 out: + fp32 residual", pre32 + res, rref, br, (1e-4, 2e-3))
+  reject("gemm", "fp32 out: residual added in bf16 on the fp32 stream", pre32 + rne(res), rref, br, (1e-4, 2e-3))
+
+
+# ------------------------------------------------------------------ GELU ----
+K0, K1 = B._K0, B._K1
+U0, U1 = 2 * 0.7978845608028654, 2 * 0.7978845608028654 * 3 * 0.044715
+
+
+def gelu32(h):
+  """bv_common.h's fp32 operation sequence: z = x (k0 + k1 x^2), s = 1 / (1 + 2^z), g = x s, g' = s + g (1 - s) u'."""
+  x = h.float()
+  z = x * (x * x * K1 + K0)
+  s = 1.0 / (torch.exp2(z) + 1.0)
+  g = x * s
+  dg = g * (1.0 - s) * (x * x * U1 + U0) + s
+  return g, dg
+
+
+def test_gelu_epilogue_bounds_bite():
+  """Inputs of test_gemm256_gpu.py::test_nt_epilogues (512 x 512 x 256): EPI_GELU's h and g, GELU_GD's g', and
+  GELU_BWD's dX = bf16(P o bf16(gelu'(h))) on the stored pre-activation hh, each checked stage by stage."""
+  M, N, K = 512, 512, 256
+  x = B.rnd((M, K), CPU, 8, dtype=BF16)
+  w = B.rnd((N, K), CPU, 9, 0.1, dtype=BF16)
+  b = B.rnd((N,), CPU, 10)
+  ap = B.absprod(x, w.T)
+  prod64 = x.double() @ w.double().T
+  pre64 = prod64 + b.double()
+  prod32 = x.float() @ w.float().T
+  pre32 = prod32 + b
+  h = rne(pre32)
+  accept("gelu", "h = RNE(fp32 pre)", h, pre64, B.gemm_bf16(pre64, ap, K), (1e-2, 1e-2))
+  gref, gb = B.gelu_g(h)
+  g32, dg32 = gelu32(h)
+  accept("gelu", "g = RNE(gelu_tanh(h)) in fp32", rne(g32), gref, gb, (1e-2, 1e-2))
+  reject("gelu", "erf GELU instead of the tanh form", rne(torch.nn.functional.gelu(h)), gref, gb, (1e-2, 1e-2))
+  reject("gelu", "GELU of the fp32 pre-activation instead of bf16(h)", rne(gelu32(pre32)[0]), gref, gb, (1e-2, 1e-2))
+  dref, db = B.gelu_dg(h)
+  accept("gelu", "g' = RNE(gelu_tanh'(h)) in fp32 (GELU_GD)", rne(dg32), dref, db, (1e-2, 1e-2))
+  reject("gelu", "g' of the fp32 pre-activation (GELU_GD)", rne(gelu32(pre32)[1]), dref, db, (1e-2, 1e-2))
+  hh = B.rnd((M, N), CPU, 15, dtype=BF16)
+  _, dgh = gelu32(hh)
+  lo_hi, bb = B.gelu_bwd(prod64, ap, K, hh)
+  legacy_ref = prod64 * B.dgelu_tanh64(hh)
+  accept("gelu_bwd", "dX = RNE(P o RNE(gelu'(h)))", rne(prod32 * rne(dgh)), legacy_ref, bb, (1e-2, 2e-2), lo_hi)
+  reject("gelu_bwd", "gelu'(h) not rounded to bf16 before the product", rne(prod32 * dgh), legacy_ref, bb, (1e-2, 2e-2),
+         lo_hi)
+  reject("gelu_bwd", "erf GELU' in the fused backward",
+         rne(prod32 * rne(torch.func.grad(lambda t: torch.nn.functional.gelu(t).sum())(hh.float()))), legacy_ref, bb,
+         (1e-2, 2e-2), lo_hi)
+  g_emit = rne(gelu32(hh)[0])
+  gr2, gb2 = B.gelu_g(hh)
+  accept("gelu_bwd", "EMIT: g = RNE(gelu_tanh(aux))", g_emit, gr2, gb2, (1e-2, 1e-2))
+  reject("gelu_bwd", "EMIT: erf GELU", rne(torch.nn.functional.gelu(hh.float())), gr2, gb2, (1e-2, 1e-2))
+
+
+# ------------------------------------------------------------- LayerNorm ----
+def _tree_sum(v):
+  """layernorm.hip's summation order: D / 64 values per lane, then a 6-level butterfly across the 64 lanes."""
+  rows, D = v.shape
+  pad = (-D) % 64
+  v = torch.nn.functional.pad(v, (0, pad)).view(rows, -1, 64)
+  s = torch.zeros(rows, 64)
+  for i in range(v.shape[1]):
+    s = s + v[:, i]
+  while s.shape[1] > 1:
+    s = s[:, :s.shape[1] // 2] + s[:, s.shape[1] // 2:]
+  return s
+
+
+def ln_fwd32(x, scale, bias, eps=1e-6, two_pass=False, ddof=0):
+  x = x.float(); D = x.shape[1]
+  mean = _tree_sum(x) / D
+  if two_pass:
+    var = _tree_sum((x - mean) ** 2) / (D - ddof)
+  else:
+    var = (_tree_sum(x * x) / D - mean * mean).clamp_min(0) * (D / (D - ddof))
+  rstd = torch.rsqrt(var + eps)
+  return (x - mean) * rstd * scale + bias, mean, rstd
+
+
+def ln_bwd32(dy, x, scale, mean, rstd, dres=None, drop_mean=False):
+  g = dy.float() * scale
+  xh = (x.float() - mean) * rstd
+  D = x.shape[1]
+  s1 = _tree_sum(g) / D
+  s2 = _tree_sum(g * xh) / D
+  dx = rstd * (g - (0 if drop_mean else s1) - xh * s2)
+  return dx + (dres.float() if dres is not None else 0)
+
+
+@pytest.mark.parametrize("bf16_x", [False, True], ids=["f32-stream", "bf16-stream"])
+def test_layernorm_bounds_bite(bf16_x):
+  """Inputs of test_kernels_gpu.py::test_layernorm (37 x 768) with the edge rows: mean ~0 and std 1e-2 / 1e-3, and
+  |mean| / std = 4.  Forward fp32 / bf16 outputs, backward fp32 / bf16 dx, dscale."""
+  rows, D = 37, 768
+  x = B.rnd((rows, D), CPU, 1, 2.0) + 0.5
+  written = B.ln_edge_rows(x)
+  if bf16_x:
+    x = x.to(BF16).float()
+  scale = 1 + 0.1 * B.rnd((D,), CPU, 2); bias = 0.1 * B.rnd((D,), CPU, 3)
+  fam = "ln" + ("-bf16x" if bf16_x else "")
+  ref, bf, bb = B.ln_fwd_bounds(x, scale, bias)
+  edge = torch.zeros(rows, 1, dtype=torch.bool)
+  edge[[r for r, kind in written if kind.startswith("std")]] = True   # the small-std rows
+  for name, two in (("Flax fast variance in fp32", False), ("two-pass variance in fp32", True)):
+    y, _, _ = ln_fwd32(x, scale, bias, two_pass=two)
+    accept(fam, f"y fp32: {name}", y, ref, bf, (1e-5, 1e-5))
+    accept(fam, f"y bf16: {name}", rne(y), ref, bb, (1e-2, 1e-2))
+  y5, _, _ = ln_fwd32(x, scale, bias, eps=1e-5)
+  n_plain = B.count_rejected(y5[~edge[:, 0]], ref[~edge[:, 0]], bf[~edge[:, 0]], (1e-5, 1e-5))
+  _rec(fam, "(info) eps 1e-5, rows of std ~2 only", n_plain, int((~edge).sum()) * D)
+  reject(fam, "eps 1e-5 instead of 1e-6 (y fp32)", y5, ref, bf, (1e-5, 1e-5))
+  reject(fam, "eps 1e-5 instead of 1e-6 (y bf16)", rne(y5), ref, bb, (1e-2, 1e-2))
+  yd, _, _ = ln_fwd32(x, scale, bias, ddof=1)
+  reject(fam, "variance divided by D - 1 (y fp32)", yd, ref, bf, (1e-5, 1e-5))
+  reject(fam, "variance divided by D - 1 (y bf16)", rne(yd), ref, bb, (1e-2, 1e-2))
+  # backward (fp32 dy and the residual gradient)
+  dy = B.rnd((rows, D), CPU, 4)
+  dres = B.rnd((rows, D), CPU, 5)
+  if bf16_x:
+    dres = dres.to(BF16).float()
+  _, mean, rstd = ln_fwd32(x, scale, bias)
+  dref, dbf, dbb = B.ln_bwd_bounds(x, scale, dy, dres)
+  dx = ln_bwd32(dy, x, scale, mean, rstd, dres)
+  if not bf16_x:
+    accept(fam, "dx fp32: prescribed backward", dx, dref, dbf, (1e-4, 1e-4))
+    reject(fam, "dx fp32: mean term missing", ln_bwd32(dy, x, scale, mean, rstd, dres, drop_mean=True), dref, dbf,
+           (1e-4, 1e-4))
+    _, m5, r5 = ln_fwd32(x, scale, bias, eps=1e-5)
+    reject(fam, "dx fp32: eps 1e-5 statistics", ln_bwd32(dy, x, scale, m5, r5, dres), dref, dbf, (1e-4, 1e-4))
+  accept(fam, "dx bf16: prescribed backward", rne(dx), dref, dbb, (1e-2, 1e-2))
+  reject(fam, "dx bf16: mean term missing", rne(ln_bwd32(dy, x, scale, mean, rstd, dres, drop_mean=True)), dref, dbb,
+         (1e-2, 1e-2))
+  _, m5, r5 = ln_fwd32(x, scale, bias, eps=1e-5)
+  reject(fam, "dx bf16: eps 1e-5 statistics", rne(ln_bwd32(dy, x, scale, m5, r5, dres)), dref, dbb, (1e-2, 1e-2))
+  xh = (x.double() - x.double().mean(-1, keepdim=True)) * (x.double().var(-1, unbiased=False, keepdim=True)
+                                                           + 1e-6).rsqrt()
+  ds_ref = (dy.double() * xh).sum(0)
+  xh32 = (x - mean) * rstd
+  ds = (dy * xh32).sum(0)
+  accept(fam, "dscale: sum dy x_hat", ds, ds_ref, ds_ref.abs() * 0 + 1, (1e-4, 1e-3))
+  y32, _, _ = ln_fwd32(x, scale, bias)
+  reject(fam, "dscale computed from y instead of x_hat", (dy * y32).sum(0), ds_ref, ds_ref.abs() * 0 + 1, (1e-4, 1e-3))
+
+
+def _ln_dx32(x, scale, dy, dres, chunk=4096):
+  """The fp32 dx of the LayerNorm backward (fp64 arithmetic, rounded once), in row chunks."""
+  out = []
+  for r0 in range(0, x.shape[0], chunk):
+    xs = x[r0:r0 + chunk].double()
+    mean = xs.mean(-1, keepdim=True)
+    rstd = (xs.var(-1, unbiased=False, keepdim=True) + 1e-6).rsqrt()
+    xh = (xs - mean) * rstd
+    g = dy[r0:r0 + chunk].double() * scale.double()
+    dx = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+    if dres is not None:
+      dx = dx + dres[r0:r0 + chunk].double()
+    out.append(dx.float())
+  return torch.cat(out)
+
+
+def _colsum_worst(dx32, nwg, seed, orders=40):
+  """ln_bwd_kernel's fused dx_colsum (layernorm.hip): row r goes to wave r mod 4 nwg, each wave sums its rows in
+  fp32 in row order, each workgroup adds its 4 wave partials, and the workgroup partials reach the column sums
+  (initialised to 1) by fp32 atomics in an order the hardware chooses.  Worst err / tol, tol = 1e-3 + 1e-4 |ref| (the
+  GPU tests' tolerance, ref = 1 + the fp64 sum of the fp32 dx), over `orders` random workgroup orders."""
+  rows, D = dx32.shape
+  nw = 4 * nwg
+  v = torch.nn.functional.pad(dx32, (0, 0, 0, (-rows) % nw)).view(-1, nw, D)
+  waves = torch.zeros(nw, D)
+  for i in range(v.shape[0]):
+    waves = waves + v[i]
+  w = waves.view(nwg, 4, D)
+  part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+  ref = 1.0 + dx32.double().sum(0)
+  tol = 1e-3 + 1e-4 * ref.abs()
+  gen = torch.Generator().manual_seed(seed)
+  worst = 0.0
+  for _ in range(orders):
+    acc = torch.ones(D)
+    for j in torch.randperm(nwg, generator=gen).tolist():
+      acc = acc + part[j]
+    worst = max(worst, ((acc.double() - ref).abs() / tol).max().item())
+  return worst
+
+
+@pytest.mark.parametrize("D", [1024, 1152])
+def test_ln_colsum_is_order_independent(D):
+  """The NT = 3 buckets of test_kernel_buckets_gpu.py::test_layernorm_f32_bucket (the most workgroups: 768 at D =
+  1024, 512 at D = 1152): on the inputs of the launch whose fused dx_colsum is checked (no edge rows), every order of
+  the workgroups' atomics stays well inside the colsum tolerance.  The same inputs with the edge rows (rstd ~ 700,
+  dx ~ 700) are printed for comparison: that is why the edge rows run in launches without column sums."""
+  rows = (192 << 20) // (4 * D) + 3
+  nwg = 768 if D <= 1024 else 512
+  x = B.rnd((rows, D), CPU, 1, 2.0) + 0.5
+  scale = 1 + 0.1 * B.rnd((D,), CPU, 2)
+  dy32 = B.rnd((rows, D), CPU, 4)
+  xe = x.clone()
+  B.ln_edge_rows(xe)
+  for dy in (dy32, dy32.to(BF16).float()):
+    for dres in (None, B.rnd((rows, D), CPU, 5)):
+      tag = f"D{D} rows{rows} dy {'fp32' if dy is dy32 else 'bf16'}, dres {dres is not None}"
+      worst = _colsum_worst(_ln_dx32(x, scale, dy, dres), nwg, seed=D)
+      worst_e = _colsum_worst(_ln_dx32(xe, scale, dy, dres), nwg, seed=D)
+      print(f"[colsum] {tag}: worst err/tol over 40 atomic orders {worst:.3f} (with edge rows {worst_e:.3f})")
+      assert worst < 0.5, f"{tag}: the fused column sum depends on the atomic order near its tolerance ({worst:.3f})"
+
+
+# ------------------------------------------------------------- attention ----
+def _attn32(qkv, n, L, H, Dh, lens, scale_after_round=False):
+  """fp32 forward as attention3.hip does it: S fp32, P = exp(S - max) fp32 with an fp32 row sum, bf16(P) V."""
+  q, k, v = qkv.float().view(n, L, 3, H, Dh).unbind(2)
+  sc = 1.0 / math.sqrt(Dh)
+  s = torch.einsum("nqhd,nkhd->nhqk", q, k)
+  s = (rne(s) if scale_after_round else s) * sc
+  mask = torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None]
+  s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
+  m = s.amax(-1, keepdim=True)
+  p = torch.exp(s - m)
+  l = p.sum(-1, keepdim=True)
+  o = torch.einsum("nhqk,nkhd->nqhd", rne(p), v) / l.permute(0, 2, 1, 3)
+  return rne(o.reshape(n * L, H * Dh)), (m + torch.log(l))[..., 0]
+
+
+def _attn_bwd32(qkv, d_o, n, L, H, Dh, drop_dq_tail=False, drop_dkv_tail=False):
+  """fp32 backward with bf16 P / dS operands (exact fp32 delta), dqkv rounded to bf16."""
+  q, k, v = qkv.float().view(n, L, 3, H, Dh).unbind(2)
+  do = d_o.float().view(n, L, H, Dh)
+  sc = 1.0 / math.sqrt(Dh)
+  s = torch.einsum("nqhd,nkhd->nhqk", q, k) * sc
+  p = torch.softmax(s, -1)
+  dp = torch.einsum("nqhd,nkhd->nhqk", do, v)
+  delta = (p * dp).sum(-1, keepdim=True)
+  ds = p * (dp - delta)
+  dsq = ds.clone()
+  if drop_dq_tail:
+    dsq[..., L - 1] = 0
+  dq = torch.einsum("nhqk,nkhd->nqhd", rne(dsq), k) * sc
+  dk = torch.einsum("nhqk,nqhd->nkhd", rne(ds), q) * sc
+  dv = torch.einsum("nhqk,nqhd->nkhd", rne(p), do)
+  if drop_dkv_tail:
+    dk[:, L - 1] = 0; dv[:, L - 1] = 0
+  return rne(torch.stack([dq, dk, dv], 2).reshape(n * L, 3 * H * Dh))
+
+
+@pytest.mark.parametrize("L", [197, 576])
+def test_attention_bounds_bite(L):
+  """Inputs of test_kernels_gpu.py's attention cases (qkv scaled 1.5, seed 1 / 5): o and lse against the contraction
+  model, dqkv against its (unchanged) tolerance; masked with the key-padding lengths of the masked test."""
+  n, H, Dh = 2, 1, 64
+  qkv = B.rnd((n * L, 3 * H * Dh), CPU, 5, 1.5, dtype=BF16)
+  lens = [L, L // 3]
+  o_ref, ob, lse_ref, lb = B.attn_fwd_bounds(qkv, n, L, H, Dh, lens)
+  o, lse = _attn32(qkv, n, L, H, Dh, lens)
+  fam = f"attn L{L}"
+  accept(fam, "o: fp32 softmax, bf16 P V", o, o_ref, ob, (2e-2, 2e-2))
+  accept(fam, "lse: fp32", lse, lse_ref, lb, (1e-4, 1e-3))
+  om, lm = _attn32(qkv, n, L, H, Dh, [ln + 1 if ln < L else ln for ln in lens])
+  reject(fam, "o: key mask off by one", om, o_ref, ob, (2e-2, 2e-2))
+  reject(fam, "lse: key mask off by one", lm, lse_ref, lb, (1e-4, 1e-3))
+  os_, ls_ = _attn32(qkv, n, L, H, Dh, lens, scale_after_round=True)
+  reject(fam, "o: score scale applied after rounding S to bf16", os_, o_ref, ob, (2e-2, 2e-2))
+  reject(fam, "lse: score scale applied after rounding S to bf16", ls_, lse_ref, lb, (1e-4, 1e-3))
+  # backward, unmasked (legacy tolerance 3e-2, 3e-2 max|g|)
+  qkv1 = B.rnd((n * L, 3 * H * Dh), CPU, 1, 1.5, dtype=BF16)
+  d_o = B.rnd((n * L, H * Dh), CPU, 2, dtype=BF16)
+  qr = qkv1.double().requires_grad_(True)
+  q, k, v = qr.view(n, L, 3, H, Dh).unbind(2)
+  s = torch.einsum("nqhd,nkhd->nhqk", q / 8.0, k)
+  torch.einsum("nhqk,nkhd->nqhd", torch.softmax(s, -1), v).reshape(n * L, H * Dh).backward(d_o.double())
+  g = qr.grad
+  leg = (3e-2, 3e-2 * g.abs().max().item())
+  inf = torch.full_like(g, float("inf"))
+  accept(fam, "dqkv: bf16 P / dS operands, fp32 delta", _attn_bwd32(qkv1, d_o, n, L, H, Dh), g, inf, leg)
+  reject(fam, "dQ misses the last key", _attn_bwd32(qkv1, d_o, n, L, H, Dh, drop_dq_tail=True), g, inf, leg)
+  reject(fam, "dK / dV of the last key dropped", _attn_bwd32(qkv1, d_o, n, L, H, Dh, drop_dkv_tail=True), g, inf, leg)
+
+
+# ---------------------------------------------------------------- losses ----
+def test_loss_bounds_bite_on_extreme_rows():
+  """The extreme rows the GPU loss tests gained: fp32 emulations of the stable forms pass the (unchanged) tolerances
+  against fp64; the naive forms overflow and fail."""
+  import bv_oracle as O
+  # softmax xent, logits up to +-1e3
+  logits, labels = B.softmax_xent_extreme_inputs(CPU)
+  n = logits.shape[0]
+  lr = logits.double().requires_grad_(True)
+  ref = O.softmax_xent(lr, labels.double()); ref.backward()
+
+  def xent32(lg, subtract_max=True):
+    m = lg.amax(-1, keepdim=True) if subtract_max else torch.zeros_like(lg[:, :1])
+    lse = torch.log(torch.exp(lg - m).sum(-1, keepdim=True))
+    loss = (-(labels * (lg - m)).sum(-1) + labels.sum(-1) * lse[:, 0]).sum() / n
+    dl = (torch.exp(lg - m - lse) * labels.sum(-1, keepdim=True) - labels) / n
+    return loss, dl
+  lo, dl = xent32(logits)
+  one = torch.ones(1, dtype=torch.float64)
+  accept("xent", "softmax xent: max subtracted", lo.reshape(1), ref.detach().reshape(1), one, (1e-5, 1e-6))
+  accept("xent", "softmax xent dlogits: max subtracted", dl, lr.grad, torch.ones_like(dl.double()), (1e-4, 1e-7))
+  lo2, dl2 = xent32(logits, subtract_max=False)
+  reject("xent", "softmax without subtracting the max (loss)", lo2.reshape(1), ref.detach().reshape(1), one, (1e-5, 1e-6))
+  reject("xent", "softmax without subtracting the max (dlogits)", dl2, lr.grad, torch.ones_like(dl.double()),
+         (1e-4, 1e-7))
+  # sigmoid xent, logits beyond +-90
+  logits, labels = B.sigmoid_xent_extreme_inputs(CPU)
+  n = logits.shape[0]
+  lr = logits.double().requires_grad_(True)
+  ref = O.sigmoid_xent(lr, labels.double()); ref.backward()
+
+  def sxent32(lg, naive=False):
+    if naive:
+      lp, lnp = -torch.log(1 + torch.exp(-lg)), -torch.log(1 + torch.exp(lg))
+    else:
+      sp = torch.log1p(torch.exp(-lg.abs()))
+      lp, lnp = lg.clamp(max=0) - sp, (-lg).clamp(max=0) - sp
+    return (-(labels * lp + (1 - labels) * lnp)).sum() / n
+  accept("sig-xent", "sigmoid xent: stable log-sigmoid", sxent32(logits).reshape(1), ref.detach().reshape(1), one,
+         (1e-5, 1e-5))
+  reject("sig-xent", "naive log(1 + exp(-x))", sxent32(logits, True).reshape(1), ref.detach().reshape(1), one,
+         (1e-5, 1e-5))
+  # SigLIP at t = 100, b = -10
+  zi, zt = B.siglip_extreme_inputs(CPU)
+  nn_, Bn, off = zi.shape[0], zt.shape[0], 14
+  raw = zi @ zt.T
+  m = -torch.ones(nn_, Bn); m[torch.arange(nn_), off + torch.arange(nn_)] = 1.0
+  lg64 = 100.0 * raw.double() - 10.0
+  ref = (-O.log_sigmoid(m.double() * lg64).sum(-1)).sum() / Bn
+  x = m * (100.0 * raw - 10.0)
+  assert x.min().item() < -88.8, "the SigLIP inputs must push exp(-x) beyond the fp32 range"
+  stable = ((-x).clamp_min(0) + torch.log1p(torch.exp(-x.abs()))).sum() / Bn
+  naive = torch.log(1 + torch.exp(-x)).sum() / Bn
+  accept("siglip", "SigLIP loss: max(-x, 0) + log1p(exp(-|x|))", stable.reshape(1), ref.reshape(1), one, (1e-5, 1e-6))
+  reject("siglip", "naive log(1 + exp(-x))", naive.reshape(1), ref.reshape(1), one, (1e-5, 1e-6))

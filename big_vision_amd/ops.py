@@ -4,6 +4,8 @@ PyTorch is used only for device memory and the HIP stream; every function here
 enqueues hand-written HIP kernels on torch's current stream.  There is no
 eager/PyTorch fallback: non-GPU tensors raise.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -619,6 +621,11 @@ def dropout_mask(shape, key, rate, device):
   return out.bool()
 
 
+def _sched_array(sched):
+  """This step's schedule values (python list of floats, <= 8) as the host array the optimizer entry points read."""
+  return (ctypes.c_float * len(sched))(*[float(v) for v in sched])
+
+
 def sqnorm_(x, out):
   """out (f64[1]) += sum(x^2)."""
   _chk(x, F32, "sqnorm.x")
@@ -629,8 +636,7 @@ def sqnorm_(x, out):
 def adam_step_(params, grads, mu, nu, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, b1, b2,
                eps, bc1, bc2, stats):
   """segs: device int32/float32 table of bv_adam_seg; sched: python list of floats (<= 8)."""
-  import ctypes
-  arr = (ctypes.c_float * len(sched))(*[float(v) for v in sched])
+  arr = _sched_array(sched)
   _lib.call("bv_adam_step", _p(params), _p(grads), _p(mu), int(mu.dtype == BF16), _p(nu), _p(shadow),
             _p(segs), _p(chunk_seg), count, ctypes.cast(arr, ctypes.c_void_p), len(sched), _p(gsq),
             float(clip_norm or 0.0), float(b1), float(b2), float(eps), float(bc1), float(bc2),
@@ -641,8 +647,7 @@ def trace_step_(params, grads, trace, shadow, segs, chunk_seg, count, sched, gsq
                 stats):
   """The fused chain with optax.trace (trace: bf16 or fp32 accumulator) or, trace=None, optax.identity
   (bv_trace_step); segs / chunk_seg / sched as adam_step_."""
-  import ctypes
-  arr = (ctypes.c_float * len(sched))(*[float(v) for v in sched])
+  arr = _sched_array(sched)
   _lib.call("bv_trace_step", _p(params), _p(grads), _p(trace), int(trace is not None and trace.dtype == BF16),
             _p(shadow), _p(segs), _p(chunk_seg), count, ctypes.cast(arr, ctypes.c_void_p), len(sched), _p(gsq),
             float(clip_norm or 0.0), float(momentum), int(bool(nesterov)), _p(stats), _stream())
@@ -651,7 +656,6 @@ def trace_step_(params, grads, trace, shadow, segs, chunk_seg, count, sched, gsq
 def adafactor_leaf_(params, grads, momentum, shadow, view, state, factored, gsq, clip_norm, decay, eps, mom,
                     lr_eff, wd, sched, stats):
   """One leaf of the fused Adafactor step (bv_adafactor_leaf); view: ctypes array of 9 longs (host)."""
-  import ctypes
   _lib.call("bv_adafactor_leaf", _p(params), _p(grads), _p(momentum),
             int(momentum is not None and momentum.dtype == BF16), _p(shadow),
             ctypes.cast(view, ctypes.c_void_p), _p(state), int(factored), _p(gsq), float(clip_norm or 0.0),
@@ -663,8 +667,7 @@ def adafactor_step_(params, grads, momentum, shadow, leaves, nleaves, max_rows, 
   """The whole Adafactor step in four launches (bv_adafactor_step); leaves: device uint8 tensor holding the
   bv_af_leaf table; sched: python list of this step's schedule values (<= 8).  block_rms_clip > 0 (with block_usq, a
   float64 scratch of nleaves elements): optax.clip_by_block_rms per leaf (one more launch)."""
-  import ctypes
-  arr = (ctypes.c_float * len(sched))(*[float(v) for v in sched])
+  arr = _sched_array(sched)
   _lib.call("bv_adafactor_step", _p(params), _p(grads), _p(momentum),
             int(momentum is not None and momentum.dtype == BF16), _p(shadow), _p(leaves), int(nleaves), int(max_rows),
             int(max_cols), int(max_b), int(max_total), _p(state), _p(gsq), float(clip_norm or 0.0), float(decay),

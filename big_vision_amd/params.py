@@ -252,7 +252,7 @@ class ParamStore:
     `master_small`: every entry a kernel reads in fp32 (everything that is not a `.../kernel`: biases, LayerNorm,
     position / token embeddings, cls, t, b) and every frozen tensor, replicated.  The full flat master is released.
     Matmul kernels reach the GEMMs through the replicated bf16 shadow, which the sharded optimizer step all-gathers
-    (optax.Optimizer._sharded_adam_step); `exchange_small_` carries the updated fp32 of the replicated entries.
+    (optax.Optimizer.step); `exchange_small_` carries the updated fp32 of the replicated entries.
     slices are S apart (a whole number of 1024-element chunks) - or, with `bounds` (rank r owns [bounds[r],
     bounds[r + 1]): the sharded Adafactor cuts the flat buffer at TENSOR boundaries, its statistics are per tensor),
     of unequal length and exchanged by one broadcast per owner instead of an all-gather."""

@@ -87,7 +87,7 @@ def test_sharded_master_round_trips(world):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_master_cut_at_tensor_boundaries_round_trips(world):
-  """The sharded Adafactor owns whole tensors (optax.Optimizer._init_adafactor): unequal runs, exchanged by one
+  """The sharded Adafactor owns whole tensors (optax.Adafactor._cut): unequal runs, exchanged by one
   broadcast per owner (`bounds`) instead of the equal-slice all-gather."""
   stores = _stores(world)
   ref = stores[0].master.clone()

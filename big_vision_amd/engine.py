@@ -18,9 +18,11 @@ bf16 (fp32 MFMA accumulate).  No autograd graph is built.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
+import threading
 import weakref
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -133,8 +135,6 @@ def map_entries(prefix, D, H, M):
 # halves the LayerNorm traffic and the +residual GEMM epilogues; measured against the parity bounds
 # by tools/bf16_residual_budget.py (oracle) and the -m gpu step tests.  Everything outside
 # Encoder.fwd / Encoder.bwd sees fp32 tensors in both modes.
-import threading
-
 _tls = threading.local()   # per host thread: two trainers driving two streams from two threads do not race
 
 
@@ -151,6 +151,25 @@ def set_residual_stream(dtype):
 
 def residual_stream():
   return getattr(_tls, "stream", F32)
+
+
+# What a saved context holds (BlockCtx below): everything, everything but gelu(h), or neither gelu(h) nor the
+# LayerNorm outputs.  "Keep no context" is None.
+FULL, NO_GELU, LIGHT = KINDS = ("full", "g", "light")
+
+
+def ctx_kind(v, light_flag=False):
+  """The canonical context kind (None | FULL | NO_GELU | LIGHT) of whatever a caller or a config passes: one of the
+  three names, or a flag.  As the `save` of an executor's forward the flag asks for contexts at all (True = FULL,
+  False / None = none); as config.microbatch_light (light_flag=True) it asks for LIGHT ones (True = LIGHT, False /
+  None = FULL).  Nothing else in the package translates between these spellings."""
+  if isinstance(v, str):
+    if v not in KINDS:
+      raise ValueError(f"unknown context kind {v!r} (one of {KINDS}, True or False)")
+    return v
+  if light_flag:
+    return LIGHT if v else FULL
+  return FULL if v else None
 
 
 class _W:
@@ -270,8 +289,8 @@ def refresh_twins(store):
 
 
 def record_stream_tree(obj, stream):
-  """`record_stream(stream)` on every CUDA tensor inside a saved context (tuples / lists / dicts / objects with
-  __dict__): the allocator must not hand the blocks back to the pool of the stream that produced them while
+  """`record_stream(stream)` on every CUDA tensor inside a saved context (tuples / lists / dicts / the slotted context
+  records below / objects with __dict__): the allocator must not hand the blocks back to the pool of the stream that produced them while
   `stream` still reads them."""
   seen = set()
 
@@ -288,6 +307,9 @@ def record_stream_tree(obj, stream):
     elif isinstance(o, dict):
       for v in o.values():
         walk(v)
+    elif dataclasses.is_dataclass(o) and not isinstance(o, type):   # (slotted records have no __dict__)
+      for f in dataclasses.fields(o):
+        walk(getattr(o, f.name))
     elif hasattr(o, "__dict__") and not isinstance(o, (type, _W)):
       walk(vars(o))
 
@@ -413,69 +435,145 @@ class LN:
 
 
 class MLP:
-  def __init__(self, store, prefix, D, M):
-    self.w1 = _W(store, f"{prefix}/Dense_0/kernel"); self.b1 = _W(store, f"{prefix}/Dense_0/bias")
-    self.w2 = _W(store, f"{prefix}/Dense_1/kernel"); self.b2 = _W(store, f"{prefix}/Dense_1/bias")
+  def __init__(self, store, prefix, D, M, names=("Dense_0", "Dense_1")):
+    """names: leaf names of the two Dense layers below `prefix` (Flax MlpBlock; flaxformer's BERT calls them wi / wo)."""
+    fc1, fc2 = names
+    self.w1 = _W(store, f"{prefix}/{fc1}/kernel"); self.b1 = _W(store, f"{prefix}/{fc1}/bias")
+    self.w2 = _W(store, f"{prefix}/{fc2}/kernel"); self.b2 = _W(store, f"{prefix}/{fc2}/bias")
     self.M = M
 
   def fwd_drop(self, y_bf, resid, rate, k_gelu, k_out, keep_branch=False):
-    """resid + drop(fc2(drop(gelu(fc1(y))))) (models/vit.py:72-77,109) on the fp32 stream; returns (out, hd, g, branch)
-    in the form of full contexts: g = drop(gelu(h)) is fc2's operand and hd = gelu'(h) scaled by the SAME keep bits, so
-    the unchanged backward (dW2 = g^T dout, dH = (dout W2^T) o hd, BV_EPI_MUL) differentiates the dropped activation.
+    """resid + drop(fc2(drop(gelu(fc1(y))))) (models/vit.py:72-77,109) on the fp32 stream; returns (out, dgelu, g, branch)
+    in the form of full contexts: g = drop(gelu(h)) is fc2's operand and dgelu = gelu'(h) scaled by the SAME keep bits, so
+    the unchanged backward (dW2 = g^T dout, dH = (dout W2^T) o dgelu, BV_EPI_MUL) differentiates the dropped activation.
     branch: the MLP output BEFORE its dropout (the reference's out["mlp"], vit.py:108) when keep_branch, else None."""
     g = torch.empty((y_bf.shape[0], self.M), device=y_bf.device, dtype=BF16)
-    hd = torch.empty_like(g)
-    linear_fwd(y_bf, self.w1, self.b1, out=g, epilogue=ops.EPI_GELU_GD, out2=hd)
-    ops.dropout_bf16_(g, k_gelu, rate, b=hd)
+    dgelu = torch.empty_like(g)
+    linear_fwd(y_bf, self.w1, self.b1, out=g, epilogue=ops.EPI_GELU_GD, out2=dgelu)
+    ops.dropout_bf16_(g, k_gelu, rate, b=dgelu)
     branch = linear_fwd(g, self.w2, self.b2, out_dtype=F32)
     if keep_branch:
-      return ops.dropout_f32(branch, k_out, rate, addend=resid), hd, g, branch
-    return ops.dropout_f32(branch, k_out, rate, addend=resid, out=branch), hd, g, None
+      return ops.dropout_f32(branch, k_out, rate, addend=resid), dgelu, g, branch
+    return ops.dropout_f32(branch, k_out, rate, addend=resid, out=branch), dgelu, g, None
 
-  def fwd(self, y_bf, resid, keep_g=True, ctx=True):
-    """resid + fc2(gelu(fc1(y))) ; returns (out, hd bf16, g bf16 or None).
+  def fwd(self, y_bf, resid, kind=FULL):
+    """resid + fc2(gelu(fc1(y))); returns (out, h, dgelu, g): what a context of `kind` keeps of the hidden layer (bf16
+    [rows, M] each), the rest None.
 
-    ctx = False (a forward that saves nothing: a frozen tower, inference): fc1's epilogue writes gelu(h) only
-    (BV_EPI_GELU_G, bit-identical to the activation the saving epilogues write) and (out, None, None) is returned.
-
-    keep_g (full contexts): the fc1 epilogue BV_EPI_GELU_GD evaluates gelu AND its derivative on the fp32
-    pre-activation - they share the exp / rcp - and writes g = gelu(h) and hd = gelu'(h); the pre-activation
-    itself is never stored and the backward's fc2 dX GEMM only multiplies by hd (BV_EPI_MUL).
-    not keep_g (light contexts): hd = the bf16 pre-activation h (BV_EPI_GELU: g is applied to the rounded h
-    that is stored) and g is dropped after fc2; the backward re-derives both g and gelu'(h) from h
-    (BV_EPI_GELU_BWD_EMIT, bit-identical g)."""
-    if not ctx:
+    kind None (a forward that saves nothing: a frozen tower, inference): fc1's epilogue writes gelu(h) only
+    (BV_EPI_GELU_G, bit-identical to the activation the saving epilogues write); h = dgelu = g = None.
+    FULL: the fc1 epilogue BV_EPI_GELU_GD evaluates gelu AND its derivative on the fp32 pre-activation - they share the
+    exp / rcp - and writes g = gelu(h) and dgelu = gelu'(h); the pre-activation itself is never stored and the
+    backward's fc2 dX GEMM only multiplies by dgelu (BV_EPI_MUL).
+    NO_GELU / LIGHT: h = the bf16 pre-activation (BV_EPI_GELU: gelu is applied to the rounded h that is stored), g is
+    dropped after fc2; the backward re-derives both g and gelu'(h) from h (BV_EPI_GELU_BWD_EMIT, bit-identical g)."""
+    if kind is None:
       g = linear_fwd(y_bf, self.w1, self.b1, out_dtype=BF16, epilogue=ops.EPI_GELU_G)
-      return linear_fwd(g, self.w2, self.b2, out_dtype=resid.dtype, epilogue=ops.EPI_RESIDUAL, aux=resid), None, None
+      out = linear_fwd(g, self.w2, self.b2, out_dtype=resid.dtype, epilogue=ops.EPI_RESIDUAL, aux=resid)
+      return out, None, None, None
     g = torch.empty((y_bf.shape[0], self.M), device=y_bf.device, dtype=BF16)
-    if keep_g:
-      hd = torch.empty_like(g)
-      linear_fwd(y_bf, self.w1, self.b1, out=g, epilogue=ops.EPI_GELU_GD, out2=hd)
+    h = dgelu = None
+    if kind == FULL:
+      dgelu = torch.empty_like(g)
+      linear_fwd(y_bf, self.w1, self.b1, out=g, epilogue=ops.EPI_GELU_GD, out2=dgelu)
     else:
-      hd = linear_fwd(y_bf, self.w1, self.b1, out_dtype=BF16, epilogue=ops.EPI_GELU, out2=g)
+      h = linear_fwd(y_bf, self.w1, self.b1, out_dtype=BF16, epilogue=ops.EPI_GELU, out2=g)
     out = linear_fwd(g, self.w2, self.b2, out_dtype=resid.dtype, epilogue=ops.EPI_RESIDUAL, aux=resid)
-    return out, hd, (g if keep_g else None)
+    return out, h, dgelu, (g if kind == FULL else None)
 
-  def bwd(self, dout_f32, dout_bf, y_bf, hd, g, bias2_done=False, dx_kw=None):
+  def bwd(self, dout_f32, dout_bf, y_bf, *, h=None, dgelu=None, g=None, bias2_done=False, dx_kw=None):
     """Returns dy (bf16) = gradient w.r.t. the MLP input y.  bias2_done: the Dense_1 bias
     gradient (column sums of dout) was already accumulated by the LayerNorm-backward kernel
-    that produced dout (bv_layernorm_bwd dx_colsum).  g given: hd = gelu'(h) from the forward (see fwd).
-    g = None ("light" context): hd = the pre-activation h; the dX GEMM that needs gelu'(h) anyway
+    that produced dout (bv_layernorm_bwd dx_colsum).  g and dgelu given (full contexts, see fwd): the fc2 dX GEMM
+    multiplies by dgelu.  h given instead (contexts without gelu(h)): that GEMM needs gelu'(h) anyway and
     re-emits the activation (BV_EPI_GELU_BWD_EMIT, bit-identical to the forward's g)."""
     # The Dense_0 bias gradient (column sums of dh) is reduced inside the same epilogue.
     if g is None:
-      g = torch.empty_like(hd)
-      dh = linear_bwd_x(dout_bf, self.w2, epilogue=ops.EPI_GELU_BWD_EMIT, aux=hd, out2=g, colsum=self.b1.grad)
+      g = torch.empty_like(h)
+      dh = linear_bwd_x(dout_bf, self.w2, epilogue=ops.EPI_GELU_BWD_EMIT, aux=h, out2=g, colsum=self.b1.grad)
       linear_bwd_w(g, dout_bf, self.w2, None if bias2_done else self.b2, dy_for_bias=dout_f32)
       del g
     else:
       linear_bwd_w(g, dout_bf, self.w2, None if bias2_done else self.b2, dy_for_bias=dout_f32)
-      dh = linear_bwd_x(dout_bf, self.w2, epilogue=ops.EPI_MUL, aux=hd, colsum=self.b1.grad)
+      dh = linear_bwd_x(dout_bf, self.w2, epilogue=ops.EPI_MUL, aux=dgelu, colsum=self.b1.grad)
     # dx_kw: epilogue of the last dX GEMM (post-LN blocks add the residual branch there, fp32 out)
     if y_bf is None:   # the caller gets y from the LayerNorm backward and runs the Dense_0 dW GEMM afterwards
       return linear_bwd_x(dh, self.w1, **(dx_kw or {})), dh
     linear_bwd_w(y_bf, dh, self.w1, None)
     return linear_bwd_x(dh, self.w1, **(dx_kw or {}))
+
+
+class Dense:
+  """A Dense layer of a tower's tail (`pre_logits`, `head`): fp32 output from a bf16 operand."""
+
+  def __init__(self, store, prefix):
+    self.w, self.b = _W(store, f"{prefix}/kernel"), _W(store, f"{prefix}/bias")
+
+  def fwd(self, x_bf):
+    return linear_fwd(x_bf, self.w, self.b, out_dtype=F32)
+
+  def bwd(self, x_bf, dy):
+    """dy fp32; accumulates the kernel / bias gradients and returns dx (fp32)."""
+    dy_bf = ops.cast_bf16(dy)
+    linear_bwd_w(x_bf, dy_bf, self.w, self.b, dy_for_bias=dy)
+    return linear_bwd_x(dy_bf, self.w, out_dtype=F32)
+
+
+# ------------------------------------------------------------- contexts ------
+# What a forward keeps for its backward.  Items a context kind does not hold are None.
+_T = torch.Tensor
+@dataclasses.dataclass(slots=True, frozen=True)
+class DropSites:
+  """Dropout of one block's forward: the rate and the keys of the two residual-branch sites (the mask behind the GELU
+  is already applied to the saved g and dgelu)."""
+  rate: float; k_sa: int; k_mlp: int
+
+
+@dataclasses.dataclass(slots=True)
+class BlockCtx:
+  """Encoder1DBlock.  x / x1: the stream entering the block / after the attention branch (fp32 or bf16: the stream
+  the context was built on); mean*, rstd*: statistics of LayerNorm_0 / LayerNorm_1; y0 / y1: their bf16 outputs (None
+  in LIGHT contexts); qkv, o, lse: attention operands, output and log-sum-exp; of the MLP's hidden layer either
+  dgelu = gelu'(h) and g = gelu(h) (FULL) or the bf16 pre-activation h (NO_GELU, LIGHT); drop: set by a forward with
+  dropout > 0."""
+  x: _T; mean0: _T; rstd0: _T; y0: Optional[_T]
+  qkv: _T; o: _T; lse: _T
+  x1: _T; mean1: _T; rstd1: _T; y1: Optional[_T]
+  h: Optional[_T] = None; dgelu: Optional[_T] = None; g: Optional[_T] = None
+  drop: Optional[DropSites] = None
+
+  @property
+  def stream(self):
+    return self.x.dtype
+
+
+@dataclasses.dataclass(slots=True)
+class MAPCtx:
+  """MAPHead: y = its input (bf16 encoder_norm output), the probe rows and their query projection q, kv, the attention
+  output o and probabilities p, a = out-projection (fp32), LayerNorm statistics and output yl, the MLP's dgelu / g."""
+  y: _T; probe_t: _T; q: _T; kv: _T; o: _T; p: _T
+  a: _T; mean: _T; rstd: _T; yl: _T; dgelu: _T; g: _T
+
+
+@dataclasses.dataclass(slots=True)
+class PostLNCtx:
+  """BERT's post-LayerNorm block (models/proj/flaxformer/bert.py): xb = the block input (bf16), attention qkv / o /
+  lse, a = x + attention branch (fp32), (m1, r1) and x1b: statistics and bf16 output of the attention LayerNorm, the
+  MLP's dgelu / g, m = x1 + MLP branch (fp32), (m2, r2): statistics of the MLP LayerNorm."""
+  xb: _T; qkv: _T; o: _T; lse: _T
+  a: _T; m1: _T; r1: _T; x1b: _T
+  dgelu: _T; g: _T; m: _T; m2: _T; r2: _T
+
+
+@dataclasses.dataclass(slots=True)
+class TailCtx:
+  """PooledTail: the encoder's contexts and output xL, encoder_norm's statistics (of all rows, or of the selected row
+  `off` of every sample), and what the pooling kind and the Dense layers keep."""
+  n: int; L: int; xL: _T; enc: list; kv_len: Optional[_T] = None
+  mean: Optional[_T] = None; rstd: Optional[_T] = None; off: int = 0
+  argmax: Optional[_T] = None; map: Optional[MAPCtx] = None
+  pre: Optional[Tuple[_T, _T]] = None     # (bf16 operand of pre_logits, its tanh output)
+  head_in: Optional[_T] = None
 
 
 # ------------------------------------------------------------- encoder -------
@@ -493,13 +591,14 @@ class Block:
     self.bo = _W(store, f"{A}/out/bias")
     self.mlp = MLP(store, f"{P}/MlpBlock_0", D, M)
 
-  def fwd(self, x, n, L, light=False, kv_len=None, drop=None, collect=False, ctx=True):
-    """kv_len (int32 [n], optional): key-padding length per sample (NaFlex, naflex_vit.py:84-113).
-    ctx = False: the caller keeps no context of this block (Encoder.fwd with save falsy): the MLP writes gelu(h) only.
-    drop (Dropout of THIS block, rate > 0): the dropout sites of vit.py:100,109 and :76, see _fwd_drop.
-    light (True, or "g" = only the second item): the saved context drops what the backward can re-derive cheaply - the two
-    LayerNorm outputs (re-normalised from x / x1) and gelu(h) (re-emitted by the fc2 dX
-    GEMM) - one third of the block's activation bytes."""
+  def fwd(self, x, n, L, kind=FULL, kv_len=None, drop=None, collect=False):
+    """Returns (x2, BlockCtx, branches).
+    kind (ctx_kind): None = the caller keeps no context of this block: the MLP writes gelu(h) only.  NO_GELU: the context
+    holds the pre-activation `h` instead of `dgelu` and `g` (gelu(h) is re-emitted by the fc2 dX GEMM).  LIGHT: also
+    without the LayerNorm outputs `y0` / `y1` (re-normalised from x / x1) - one third of the block's activation bytes.
+    kv_len (int32 [n], optional): key-padding length per sample (NaFlex, naflex_vit.py:84-113).
+    drop (Dropout of THIS block, rate > 0): the dropout sites of vit.py:100,109 and :76, see _fwd_drop; `branches` is
+    then, with `collect`, the two branch outputs before their dropout, otherwise None."""
     T, D, H = n * L, self.D, self.H
     if drop is not None and drop.rate > 0.0:
       return self._fwd_drop(x, n, L, kv_len, drop, collect)
@@ -508,18 +607,18 @@ class Block:
     o, lse = ops.attn_fwd(qkv, n, L, H, kv_len=kv_len)
     x1 = linear_fwd(o, self.wo, self.bo, out_dtype=x.dtype, epilogue=ops.EPI_RESIDUAL, aux=x)   # fp32 or bf16 stream
     y1, _, mean1, rstd1 = self.ln1.fwd(x1, T, D)
-    x2, h, g = self.mlp.fwd(y1, x1, keep_g=not light, ctx=ctx)
-    if light is True:     # light == "g": only gelu(h) is dropped, the LayerNorm outputs stay
+    x2, h, dgelu, g = self.mlp.fwd(y1, x1, kind)
+    if kind == LIGHT:
       y0 = y1 = None
-    return x2, (x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, h, g)
+    return x2, BlockCtx(x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, h, dgelu, g), None
 
   def _fwd_drop(self, x, n, L, kv_len, drop, collect=False):
     """Encoder1DBlock in train mode with dropout > 0 (vit.py:90-111): x1 = x + drop(attention branch), x2 = x1 +
     drop(MLP branch), drop(gelu(h)) inside the MLP.  fp32 stream, full contexts.  The residual adds cannot ride in
     the GEMM epilogues here: each branch GEMM writes fp32 and ONE element-wise kernel applies the mask and adds the
-    stream (bv_dropout_f32).  The context carries the site keys as a 14th entry (rate, k_sa, k_mlp, pre); pre = the
-    two branch outputs BEFORE their dropout when `collect` (the reference publishes those as out["sa"] / out["mlp"],
-    vit.py:98,108), which Encoder.fwd takes out of the context again."""
+    stream (bv_dropout_f32).  The context carries the site keys in `drop`.  With `collect` the two branch outputs
+    BEFORE their dropout are returned beside it (the reference publishes those as out["sa"] / out["mlp"],
+    vit.py:98,108); they are no part of the context."""
     if x.dtype != F32:
       raise NotImplementedError("dropout > 0 runs on the float32 residual stream only")
     T, D, H = n * L, self.D, self.H
@@ -530,65 +629,66 @@ class Block:
     branch = linear_fwd(o, self.wo, self.bo, out_dtype=F32)
     x1 = ops.dropout_f32(branch, k_sa, drop.rate, addend=x, out=None if collect else branch)
     y1, _, mean1, rstd1 = self.ln1.fwd(x1, T, D)
-    x2, hd, g, mlp_pre = self.mlp.fwd_drop(y1, x1, drop.rate, k_gelu, k_mlp, keep_branch=collect)
-    pre = (branch, mlp_pre) if collect else None
-    return x2, (x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, hd, g, (drop.rate, k_sa, k_mlp, pre))
+    x2, dgelu, g, mlp_pre = self.mlp.fwd_drop(y1, x1, drop.rate, k_gelu, k_mlp, keep_branch=collect)
+    saved = BlockCtx(x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, None, dgelu, g,
+                     DropSites(drop.rate, k_sa, k_mlp))
+    return x2, saved, ((branch, mlp_pre) if collect else None)
 
-  def _bwd_drop(self, saved, dx2, n, L, kv_len):
+  def _bwd_drop(self, c: BlockCtx, dx2, n, L, kv_len):
     """Backward of _fwd_drop.  The gradient of a dropped branch is the stream's gradient under the branch's mask:
     the bf16 operand of the branch's dX / dW GEMMs is written by the dropout kernel (instead of the LayerNorm
     backward's plain bf16 copy) and the branch biases take ITS column sums (the fused column sums of the LayerNorm
     backward would be those of the unmasked stream)."""
-    x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, hd, g, (rate, k_sa, k_mlp, _) = saved
     T, D, H = n * L, self.D, self.H
-    dmlp_bf = ops.dropout_f32(dx2, k_mlp, rate, out_bf16=torch.empty((T, D), device=dx2.device, dtype=BF16))
-    dy1 = self.mlp.bwd(None, dmlp_bf, y1, hd, g, bias2_done=False)
+    rate = c.drop.rate
+    dmlp_bf = ops.dropout_f32(dx2, c.drop.k_mlp, rate, out_bf16=torch.empty((T, D), device=dx2.device, dtype=BF16))
+    dy1 = self.mlp.bwd(None, dmlp_bf, c.y1, dgelu=c.dgelu, g=c.g, bias2_done=False)
     del dmlp_bf
-    dx1 = self.ln1.bwd(dy1, x1, mean1, rstd1, T, D, dres=dx2)
-    dsa_bf = ops.dropout_f32(dx1, k_sa, rate, out_bf16=torch.empty((T, D), device=dx2.device, dtype=BF16))
-    linear_bwd_w(o, dsa_bf, self.wo, self.bo)
+    dx1 = self.ln1.bwd(dy1, c.x1, c.mean1, c.rstd1, T, D, dres=dx2)
+    dsa_bf = ops.dropout_f32(dx1, c.drop.k_sa, rate, out_bf16=torch.empty((T, D), device=dx2.device, dtype=BF16))
+    linear_bwd_w(c.o, dsa_bf, self.wo, self.bo)
     d_o = linear_bwd_x(dsa_bf, self.wo)
     del dsa_bf
-    dqkv = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, dbias=self.bqkv.grad, kv_len=kv_len)
-    linear_bwd_w(y0, dqkv, self.wqkv, None)
+    dqkv = ops.attn_bwd(c.qkv, c.o, d_o, c.lse, n, L, H, dbias=self.bqkv.grad, kv_len=kv_len)
+    linear_bwd_w(c.y0, dqkv, self.wqkv, None)
     dy0 = linear_bwd_x(dqkv, self.wqkv)
     dx_bf = torch.empty((T, D), device=dx2.device, dtype=BF16)
-    dx = self.ln0.bwd(dy0, x, mean0, rstd0, T, D, dres=dx1, dx_bf16=dx_bf)
+    dx = self.ln0.bwd(dy0, c.x, c.mean0, c.rstd0, T, D, dres=dx1, dx_bf16=dx_bf)
     return dx, dx_bf
 
-  def bwd(self, saved, dx2, dx2_bf, n, L, b2_done=False, next_b2=None, kv_len=None):
+  def bwd(self, c: BlockCtx, dx2, dx2_bf, n, L, b2_done=False, next_b2=None, kv_len=None):
     """b2_done: this block's MlpBlock Dense_1 bias gradient was fused into the producer of dx2;
     next_b2: gradient buffer of the PREVIOUS block's Dense_1 bias, to be fused into the
     LayerNorm_0 backward that produces that block's dx2 (bias grads = column sums of dx)."""
-    if len(saved) == 14:   # saved by _fwd_drop (b2_done / next_b2 are never set for such contexts, see Encoder.bwd)
+    if c.drop is not None:   # saved by _fwd_drop (b2_done / next_b2 are never set for such contexts, see Encoder.bwd)
       assert not b2_done and next_b2 is None
-      return self._bwd_drop(saved, dx2, n, L, kv_len)
-    x, mean0, rstd0, y0, qkv, o, lse, x1, mean1, rstd1, y1, h, g = saved
+      return self._bwd_drop(c, dx2, n, L, kv_len)
     T, D, H = n * L, self.D, self.H
-    if x.dtype == BF16:   # bf16 residual stream: the gradient stream IS the GEMM operand
+    x, x1, y0, y1 = c.x, c.x1, c.y0, c.y1
+    if c.stream == BF16:   # bf16 residual stream: the gradient stream IS the GEMM operand
       dx2 = dx2_bf
     # Light contexts keep neither LayerNorm output.  On the fp32 stream the LayerNorm BACKWARD kernel re-emits
     # it (bv_layernorm_bwd_y: it reads x anyway; same expression, same bits as the forward) and the weight-
     # gradient GEMM that needs it runs right after; on the bf16 stream a forward pass re-normalises first.
-    emit_y = x.dtype == F32
+    emit_y = c.stream == F32
     if y1 is None and not emit_y:
       y1 = self.ln1.fwd(x1, T, D)[0]
     dh = None
     if y1 is None:
-      dy1, dh = self.mlp.bwd(dx2, dx2_bf, None, h, g, bias2_done=b2_done)
+      dy1, dh = self.mlp.bwd(dx2, dx2_bf, None, h=c.h, dgelu=c.dgelu, g=c.g, bias2_done=b2_done)
       y1 = torch.empty((T, D), device=dx2.device, dtype=BF16)
       y1_out = y1
     else:
-      dy1 = self.mlp.bwd(dx2, dx2_bf, y1, h, g, bias2_done=b2_done)
+      dy1 = self.mlp.bwd(dx2, dx2_bf, y1, h=c.h, dgelu=c.dgelu, g=c.g, bias2_done=b2_done)
       y1_out = None
     dx1_bf = torch.empty((T, D), device=dx2.device, dtype=BF16)
-    dx1 = self.ln1.bwd(dy1, x1, mean1, rstd1, T, D, dres=dx2, dx_bf16=dx1_bf, dx_colsum=self.bo.grad, y_out=y1_out)
+    dx1 = self.ln1.bwd(dy1, x1, c.mean1, c.rstd1, T, D, dres=dx2, dx_bf16=dx1_bf, dx_colsum=self.bo.grad, y_out=y1_out)
     if dh is not None:
       linear_bwd_w(y1, dh, self.mlp.w1, None)
     del y1, dh
-    linear_bwd_w(o, dx1_bf, self.wo, None)      # out-proj bias grad = colsum(dx1): fused above
+    linear_bwd_w(c.o, dx1_bf, self.wo, None)      # out-proj bias grad = colsum(dx1): fused above
     d_o = linear_bwd_x(dx1_bf, self.wo)
-    dqkv = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, dbias=self.bqkv.grad, kv_len=kv_len)   # q/k/v bias grads fused
+    dqkv = ops.attn_bwd(c.qkv, c.o, d_o, c.lse, n, L, H, dbias=self.bqkv.grad, kv_len=kv_len)   # q/k/v bias grads fused
     if y0 is None and not emit_y:
       y0 = self.ln0.fwd(x, T, D)[0]
     y0_out = None
@@ -598,14 +698,14 @@ class Block:
       linear_bwd_w(y0, dqkv, self.wqkv, None)
     dy0 = linear_bwd_x(dqkv, self.wqkv)
     dx_bf = torch.empty((T, D), device=dx2.device, dtype=BF16)
-    dx = self.ln0.bwd(dy0, x, mean0, rstd0, T, D, dres=dx1, dx_bf16=dx_bf, dx_colsum=next_b2, y_out=y0_out)
+    dx = self.ln0.bwd(dy0, x, c.mean0, c.rstd0, T, D, dres=dx1, dx_bf16=dx_bf, dx_colsum=next_b2, y_out=y0_out)
     if y0_out is not None:
       linear_bwd_w(y0_out, dqkv, self.wqkv, None)
     return dx, dx_bf
 
 
 class Encoder:
-  """vit.Encoder without the final encoder_norm (the caller applies it, because
+  """vit.Encoder without the final encoder_norm (PooledTail applies it, because
   which rows it must cover depends on the pooling)."""
 
   def __init__(self, store, prefix, depth, D, H, M, scan=False):
@@ -616,9 +716,10 @@ class Encoder:
 
   def fwd(self, x, n, L, save, out=None, kv_len=None, drop=None):
     """x: fp32 [n*L, D].  Returns the last block's output in the stream dtype (the callers hand it to
-    encoder_norm, whose kernel takes either) and the saved contexts.
+    encoder_norm, whose kernel takes either) and the saved contexts (a list of BlockCtx; empty when `save` asks for none).
     drop (Dropout, rate > 0; train mode of vit.py:100,109,76): every block gets its own fold of it; contexts are full
     ones whatever `save` asks for (the light kinds re-derive activations the mask would have to be re-applied to)."""
+    kind = ctx_kind(save)
     saved = []
     dropping = drop is not None and drop.rate > 0.0
     if dropping and residual_stream() == BF16:
@@ -627,18 +728,14 @@ class Encoder:
       x = ops.cast_bf16(x)
     for i, blk in enumerate(self.blocks):
       x_in = x
-      x, s = blk.fwd(x, n, L, light=(True if save == "light" else ("g" if save == "g" else False)), kv_len=kv_len,
-                     drop=(drop.fold("block", i) if dropping else None), collect=out is not None, ctx=bool(save))
-      pre = None
-      if dropping and out is not None:       # the branch outputs before their dropout leave the context again
-        pre, s = s[13][3], s[:13] + (s[13][:3] + (None,),)
-      if save:
-        saved.append(s)
+      x, c, branches = blk.fwd(x, n, L, kind, kv_len=kv_len, drop=(drop.fold("block", i) if dropping else None),
+                               collect=out is not None)
+      if kind is not None:
+        saved.append(c)
       if out is not None:
-        x1 = s[7]
         v = lambda t: t.view(n, L, -1)   # the reference's activations are [n, L, D]
-        sa, mlp = pre if pre is not None else (x1 - x_in, x - x1)     # (vit.py:98,108: published BEFORE the dropout)
-        out[f"block{i:02d}"] = {"sa": v(sa), "+sa": v(x1), "mlp": v(mlp), "+mlp": v(x)}
+        sa, mlp = branches if branches is not None else (c.x1 - x_in, x - c.x1)     # (vit.py:98,108: published BEFORE the dropout)
+        out[f"block{i:02d}"] = {"sa": v(sa), "+sa": v(c.x1), "mlp": v(mlp), "+mlp": v(x)}
     if out is not None and not self.scan:   # (the reference's scan branch publishes no `pre_ln` alias, vit.py:129-157)
       out["pre_ln"] = x.view(n, L, -1)
     return x, saved
@@ -646,34 +743,34 @@ class Encoder:
   @staticmethod
   def dropped(saved):
     """True for contexts saved by a forward with dropout > 0 (Block._fwd_drop)."""
-    return bool(saved) and len(saved[0]) == 14
+    return bool(saved) and saved[0].drop is not None
 
-  def last_b2_grad(self, saved=None):
-    """Gradient buffer of the last block's Dense_1 bias: the kernel that produces the
-    encoder's incoming dx (encoder_norm backward) accumulates its column sums there.  None for contexts saved under
-    dropout: that bias takes the column sums of the MASKED gradient (Block._bwd_drop)."""
-    if saved is not None and self.dropped(saved):
-      return None
-    return self.blocks[-1].mlp.b2.grad if self.blocks else None
-
-  def bwd(self, saved, dx, dx_bf, n, L, b2_done=False, on_block=None, kv_len=None):
-    """on_block(i): called after block i's backward is enqueued; the gradients of blocks >= i
+  def bwd(self, saved, dx, dx_bf, n, L, on_block=None, kv_len=None):
+    """dx / dx_bf: the gradient of the last block's output as encoder_norm's backward leaves it (PooledTail.bwd).
+    on_block(i): called after block i's backward is enqueued; the gradients of blocks >= i
     are final at that point (block i's Dense_1 bias was accumulated earlier, by the kernel
     that produced its incoming dx; block i's backward also finishes block i-1's Dense_1 bias)."""
-    last = len(self.blocks) - 1
-    bf_stream = bool(saved) and saved[0][0].dtype == BF16   # the contexts remember the stream they were built on
-    dropped = self.dropped(saved)
-    assert not (dropped and b2_done), "contexts saved under dropout: the caller must not fuse the Dense_1 bias gradient"
-    for i in range(last, -1, -1):
-      nb2 = self.blocks[i - 1].mlp.b2.grad if (i > 0 and not dropped) else None
-      dx, dx_bf = self.blocks[i].bwd(saved[i], dx, dx_bf, n, L,
-                                     b2_done=(False if dropped else (b2_done if i == last else True)),
-                                     next_b2=nb2, kv_len=kv_len)
+    bf_stream = bool(saved) and saved[0].stream == BF16   # the contexts remember the stream they were built on
+    fused = self.fuses_b2(saved)
+    for i in range(len(self.blocks) - 1, -1, -1):
+      nb2 = self.blocks[i - 1].mlp.b2.grad if (i > 0 and fused) else None
+      dx, dx_bf = self.blocks[i].bwd(saved[i], dx, dx_bf, n, L, b2_done=fused, next_b2=nb2, kv_len=kv_len)
       if on_block is not None:
         on_block(i)
     if bf_stream:   # callers (stem / embedding / posemb gradients) take the fp32 tensor and its bf16 copy
       dx = ops.cast_f32(dx_bf)
     return dx, dx_bf
+
+  def fuses_b2(self, saved):
+    """Is every block's Dense_1 bias gradient (column sums of the block's incoming dx) summed by the kernel that PRODUCES
+    that dx - the next block's LayerNorm_0 backward, and for the last block encoder_norm's backward?  The one place
+    this is decided: not for contexts saved under dropout, whose bias takes the column sums of the MASKED gradient
+    (Block._bwd_drop)."""
+    return not self.dropped(saved)
+
+  def last_b2_grad(self, saved):
+    """Where the producer of the encoder's incoming dx accumulates its column sums (see fuses_b2), or None."""
+    return self.blocks[-1].mlp.b2.grad if (self.blocks and self.fuses_b2(saved)) else None
 
 
 # ------------------------------------------------------------- MAP head ------
@@ -698,22 +795,107 @@ class MAPHead:
     o, p = ops.map_attn_fwd(q, kv, n, L, H, kv_len=kv_len)
     a = linear_fwd(o, self.wo, self.bo, out_dtype=F32)
     yl, _, mean, rstd = self.ln.fwd(a, n, D)
-    z, h, g = self.mlp.fwd(yl, a)
-    return z, (y_bf, probe_t, q, kv, o, p, a, mean, rstd, yl, h, g)
+    z, _, dgelu, g = self.mlp.fwd(yl, a)
+    return z, MAPCtx(y_bf, probe_t, q, kv, o, p, a, mean, rstd, yl, dgelu, g)
 
-  def bwd(self, saved, dz, n, L):
-    y_bf, probe_t, q, kv, o, p, a, mean, rstd, yl, h, g = saved
+  def bwd(self, c: MAPCtx, dz, n, L):
     D, H = self.D, self.H
     dz_bf = ops.cast_bf16(dz)
-    dyl = self.mlp.bwd(dz, dz_bf, yl, h, g)
+    dyl = self.mlp.bwd(dz, dz_bf, c.yl, dgelu=c.dgelu, g=c.g)
     da_bf = torch.empty((n, D), device=dz.device, dtype=BF16)
-    da = self.ln.bwd(dyl, a, mean, rstd, n, D, dres=dz, dx_bf16=da_bf, dx_colsum=self.bo.grad)
-    linear_bwd_w(o, da_bf, self.wo, None)       # out-proj bias grad fused into the LN backward
+    da = self.ln.bwd(dyl, c.a, c.mean, c.rstd, n, D, dres=dz, dx_bf16=da_bf, dx_colsum=self.bo.grad)
+    linear_bwd_w(c.o, da_bf, self.wo, None)       # out-proj bias grad fused into the LN backward
     d_o = linear_bwd_x(da_bf, self.wo)
-    dq, dkv = ops.map_attn_bwd(q, kv, p, d_o, n, L, H)
-    linear_bwd_w(probe_t, dq, self.wq, self.bq)
+    dq, dkv = ops.map_attn_bwd(c.q, c.kv, c.p, d_o, n, L, H)
+    linear_bwd_w(c.probe_t, dq, self.wq, self.bq)
     if self.probe.grad is not None:
       dprobe_t = linear_bwd_x(dq, self.wq)
       ops.colsum(dprobe_t, self.probe.grad.view(-1))
-    linear_bwd_w(y_bf, dkv, self.wkv, self.bkv)
+    linear_bwd_w(c.y, dkv, self.wkv, self.bkv)
     return linear_bwd_x(dkv, self.wkv)   # dy (bf16 [T, D])
+
+
+# ---------------------------------------------------------- pooled tail ------
+class PooledTail:
+  """What every tower runs behind its encoder blocks, forward and backward: encoder_norm -> pooling -> (pre_logits =
+  tanh(Dense)) -> (head) (vit.py:239-274, naflex_vit.py:262-285, text_transformer.py:77-98).
+
+  pool: "map" (MAPHead), "gap" (mean), "max", "row" (one token of every sample: `row` = 0 for the first / cls token,
+  -1 for the last; encoder_norm then runs on those n rows only) or "none" (no pooling, forward only).
+  row_bf16: the selected-row LayerNorm also writes the bf16 operand of the head (the text tower; the ViT casts it
+  afterwards).  The backward ends in the encoder's: the bias gradient of the last block's Dense_1 is summed by
+  encoder_norm's backward exactly when Encoder.bwd expects it there (Encoder.fuses_b2)."""
+
+  def __init__(self, store, prefix, enc: Encoder, pool, H, M, rep_size=False, num_classes=None, row=0, row_bf16=False):
+    if pool not in ("map", "gap", "max", "row", "none"):
+      raise ValueError(f"Unknown pool type: '{pool}'")
+    self.enc, self.pool, self.row, self.row_bf16 = enc, pool, row, row_bf16
+    self.map = MAPHead(store, f"{prefix}MAPHead_0", enc.D, H, M) if pool == "map" else None
+    self.pre = Dense(store, f"{prefix}pre_logits") if rep_size else None      # vit.py:259-262
+    self.head = Dense(store, f"{prefix}head") if num_classes else None
+
+  def fwd(self, xL, saved, n, L, kv_len=None, want_encoded=False):
+    """xL, saved: what Encoder.fwd returned.  kv_len (int32 [n]): only the first kv_len[b] tokens of sample b are
+    pooled (NaFlex).  Returns (x, outs, TailCtx): outs has "head_input", "pre_logits", "logits" (with a head) and
+    "encoded" = the fp32 encoder_norm output [n*L, D] where the pooling produced it or `want_encoded` (diagnostics)
+    asks for it."""
+    D, T, norm = self.enc.D, n * L, self.enc.norm
+    if self.pool == "none" and saved:
+      raise NotImplementedError("pool_type='none' is forward-only on the accelerated path")
+    c = TailCtx(n, L, xL, saved, kv_len)
+    outs, zb = {}, None
+    if self.pool == "map":
+      y, _, c.mean, c.rstd = norm.fwd(xL, T, D)
+      z, c.map = self.map.fwd(y, n, L, kv_len=kv_len)
+      if want_encoded:
+        outs["encoded"] = norm.fwd(xL, T, D, want_bf16=False, want_f32=True)[1]
+    elif self.pool == "row" and not want_encoded:
+      c.off = self.row % L
+      zb, z, c.mean, c.rstd = norm.fwd(xL, n, D, row_stride=L, row_offset=c.off, want_bf16=self.row_bf16, want_f32=True)
+    else:
+      _, yf, c.mean, c.rstd = norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
+      outs["encoded"] = z = yf
+      if self.pool == "gap":
+        z = ops.pool_gap_fwd(yf, n, L, D, lens=kv_len)
+      elif self.pool == "max":
+        z, c.argmax = ops.pool_max_fwd(yf, n, L, D, lens=kv_len)
+      elif self.pool == "row":   # all tokens are wanted too: normalise them all and take the row
+        c.off = self.row % L
+        z = yf.view(n, L, D)[:, c.off].contiguous()
+        c.mean, c.rstd = (t.view(n, L)[:, c.off].contiguous() for t in (c.mean, c.rstd))
+    outs["head_input"] = z
+    if self.pre is not None:
+      zb0, zb = ops.cast_bf16(z), None
+      z = ops.tanh_fwd(self.pre.fwd(zb0))
+      c.pre = (zb0, z)
+    outs["pre_logits"] = x = z
+    if self.head is not None:
+      c.head_in = zb if zb is not None else ops.cast_bf16(z)
+      outs["logits"] = x = self.head.fwd(c.head_in)
+    return x, outs, c
+
+  def bwd(self, c: TailCtx, dx, on_block=None):
+    """dx: gradient of what fwd returned.  Returns the encoder's (dx0 fp32, dx0 bf16): the gradient of its input."""
+    n, L, xL = c.n, c.L, c.xL
+    D, T, norm = self.enc.D, n * L, self.enc.norm
+    dz = dx.contiguous()
+    if self.head is not None:
+      dz = self.head.bwd(c.head_in, dz)
+    if self.pre is not None:
+      zb0, y = c.pre
+      dz = self.pre.bwd(zb0, ops.tanh_bwd(y, dz.contiguous()))
+    b2 = self.enc.last_b2_grad(c.enc)
+    dxL_bf = torch.empty((T, D), device=xL.device, dtype=BF16)
+    if self.pool == "row":
+      dxL = torch.zeros((T, D), device=xL.device, dtype=F32)
+      dxL_bf.zero_()
+      norm.bwd(dz, xL, c.mean, c.rstd, n, D, dx=dxL, dx_bf16=dxL_bf, row_stride=L, row_offset=c.off, dx_colsum=b2)
+    else:
+      if self.pool == "map":
+        dy = self.map.bwd(c.map, dz, n, L)          # (masked pooling: works from the saved, masked probabilities)
+      elif self.pool == "max":
+        dy = ops.pool_max_bwd(dz, c.argmax, n, L, D)
+      else:
+        dy = ops.pool_gap_bwd(dz, n, L, D, lens=c.kv_len)
+      dxL = norm.bwd(dy, xL, c.mean, c.rstd, T, D, dx_bf16=dxL_bf, dx_colsum=b2)
+    return self.enc.bwd(c.enc, dxL, dxL_bf, n, L, on_block=on_block, kv_len=c.kv_len)

@@ -63,40 +63,36 @@ class _PostLNBlock:
     self.bo = E._W(store, f"{A}/out/bias")
     self.ln1 = E.LN(store, f"{P}/attention_block/layer_norm")
     self.ln2 = E.LN(store, f"{P}/mlp_block/layer_norm")
-    self.mlp = E.MLP.__new__(E.MLP)
-    self.mlp.w1 = E._W(store, f"{P}/mlp_block/mlp/wi/kernel"); self.mlp.b1 = E._W(store, f"{P}/mlp_block/mlp/wi/bias")
-    self.mlp.w2 = E._W(store, f"{P}/mlp_block/mlp/wo/kernel"); self.mlp.b2 = E._W(store, f"{P}/mlp_block/mlp/wo/bias")
-    self.mlp.M = M
+    self.mlp = E.MLP(store, f"{P}/mlp_block/mlp", D, M, names=("wi", "wo"))
 
   def fwd(self, xb, xf, n, L, lens):
     """xb / xf: the block input as bf16 GEMM operand and as fp32 residual (both come out of the previous
-    LayerNorm kernel).  Returns (x2b, x2f, saved)."""
+    LayerNorm kernel).  Returns (x2b, x2f, engine.PostLNCtx)."""
     T, D, H = n * L, self.D, self.H
     qkv = E.linear_fwd(xb, self.wqkv, self.bqkv, out_dtype=BF16)
     o, lse = ops.attn_fwd(qkv, n, L, H, kv_len=lens)
     a = E.linear_fwd(o, self.wo, self.bo, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=xf)
     x1b, x1f, m1, r1 = self.ln1.fwd(a, T, D, want_f32=True, eps=LN_EPS)
-    m, hd, g = self.mlp.fwd(x1b, x1f)
+    m, _, dgelu, g = self.mlp.fwd(x1b, x1f)
     x2b, x2f, m2, r2 = self.ln2.fwd(m, T, D, want_f32=True, eps=LN_EPS)
-    return x2b, x2f, (xb, qkv, o, lse, a, m1, r1, x1b, hd, g, m, m2, r2)
+    return x2b, x2f, E.PostLNCtx(xb, qkv, o, lse, a, m1, r1, x1b, dgelu, g, m, m2, r2)
 
-  def bwd(self, saved, dx2, n, L, lens):
+  def bwd(self, c: E.PostLNCtx, dx2, n, L, lens):
     """dx2: fp32 cotangent of this block's output (GEMM-operand and residual uses summed).  Returns the
     fp32 cotangent of the block input."""
-    xb, qkv, o, lse, a, m1, r1, x1b, hd, g, m, m2, r2 = saved
     T, D, H = n * L, self.D, self.H
     dev = dx2.device
     dm_bf = torch.empty((T, D), device=dev, dtype=BF16)
-    dm = self.ln2.bwd(dx2, m, m2, r2, T, D, dx_bf16=dm_bf, dx_colsum=self.mlp.b2.grad)   # wo bias grad = colsum(dm)
+    dm = self.ln2.bwd(dx2, c.m, c.m2, c.r2, T, D, dx_bf16=dm_bf, dx_colsum=self.mlp.b2.grad)   # wo bias grad = colsum(dm)
     # gradient w.r.t. x1 = MLP branch (the last dX GEMM) + residual branch dm, summed in that GEMM's epilogue
-    dx1 = self.mlp.bwd(dm, dm_bf, x1b, hd, g, bias2_done=True,
+    dx1 = self.mlp.bwd(dm, dm_bf, c.x1b, dgelu=c.dgelu, g=c.g, bias2_done=True,
                        dx_kw=dict(out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=dm))
     da_bf = torch.empty((T, D), device=dev, dtype=BF16)
-    da = self.ln1.bwd(dx1, a, m1, r1, T, D, dx_bf16=da_bf, dx_colsum=self.bo.grad)      # out-proj bias grad
-    E.linear_bwd_w(o, da_bf, self.wo, None)
+    da = self.ln1.bwd(dx1, c.a, c.m1, c.r1, T, D, dx_bf16=da_bf, dx_colsum=self.bo.grad)      # out-proj bias grad
+    E.linear_bwd_w(c.o, da_bf, self.wo, None)
     d_o = E.linear_bwd_x(da_bf, self.wo)
-    dqkv = ops.attn_bwd(qkv, o, d_o, lse, n, L, H, dbias=self.bqkv.grad, kv_len=lens)
-    E.linear_bwd_w(xb, dqkv, self.wqkv, None)
+    dqkv = ops.attn_bwd(c.qkv, c.o, d_o, c.lse, n, L, H, dbias=self.bqkv.grad, kv_len=lens)
+    E.linear_bwd_w(c.xb, dqkv, self.wqkv, None)
     return E.linear_bwd_x(dqkv, self.wqkv, out_dtype=F32, epilogue=ops.EPI_RESIDUAL, aux=da)
 
 
@@ -113,9 +109,7 @@ class BertExec:
     self.seg = E._W(store, f"{B}/embedder/embedders_segment_ids/embedding")
     self.ln = E.LN(store, f"{B}/layer_norm")
     self.blocks = [_PostLNBlock(store, f"{B}/encoder_block_{i}", D, H, M) for i in range(c["num_hidden_layers"])]
-    self.head = None
-    if m.num_classes:
-      self.head = (E._W(store, f"{prefix}head/kernel"), E._W(store, f"{prefix}head/bias"))
+    self.head = E.Dense(store, f"{prefix}head") if m.num_classes else None
     self._mask_checked = False
 
   def _lengths(self, ids):
@@ -187,7 +181,7 @@ class BertExec:
     ctx = dict(n=n, L=L, ids=ids, lens=lens, emb=(e, mean0, rstd0), blocks=saved)
     if self.head is not None:
       zb = xb.view(n, L, D)[:, 0].contiguous()
-      x = E.linear_fwd(zb, self.head[0], self.head[1], out_dtype=F32)
+      x = self.head.fwd(zb)
       out["logits"] = x
       ctx["head_in"] = zb
     return x, out, (ctx if save else None)
@@ -198,9 +192,7 @@ class BertExec:
     T = n * L
     dz = dx.contiguous()
     if self.head is not None:
-      dzb = ops.cast_bf16(dz)
-      E.linear_bwd_w(ctx["head_in"], dzb, self.head[0], self.head[1], dy_for_bias=dz)
-      dz = E.linear_bwd_x(dzb, self.head[0], out_dtype=F32)
+      dz = self.head.bwd(ctx["head_in"], dz)
     dxl = torch.zeros((n, L, D), device=dz.device, dtype=F32)   # only the CLS rows carry a cotangent
     dxl[:, 0] = dz
     dxl = dxl.view(T, D)

@@ -67,9 +67,7 @@ class NaflexExec:
     self.ln_pre = E.LN(store, f"{prefix}patchln_pre") if m.patchln_pre else None
     self.ln_post = E.LN(store, f"{prefix}patchln_post") if m.patchln_post else None
     self.enc = E.Encoder(store, f"{prefix}Transformer", m.depth, D, H, M, scan=getattr(m, "scan", False))
-    self.map = E.MAPHead(store, f"{prefix}MAPHead_0", D, H, M) if m.pool_type == "map" else None
-    self.pre = (E._W(store, f"{prefix}pre_logits/kernel"), E._W(store, f"{prefix}pre_logits/bias")) if m.rep_size else None
-    self.head = (E._W(store, f"{prefix}head/kernel"), E._W(store, f"{prefix}head/bias")) if m.num_classes else None
+    self.tail = E.PooledTail(store, prefix, self.enc, m.pool_type, H, M, rep_size=m.rep_size, num_classes=m.num_classes)
     self.patch_dim = patch_dim
     self._mask_checked = False
 
@@ -106,7 +104,7 @@ class NaflexExec:
       patches = torch.gather(patches, 1, perm[:, :, None].expand(-1, -1, pd))
       yabs, xabs = torch.gather(yabs, 1, perm), torch.gather(xabs, 1, perm)
     x_in = patches.to(F32).contiguous().view(T, pd)
-    ctx = dict(n=n, N=N, lens=lens)
+    ctx = dict(n=n, N=N)
     if self.ln_pre is not None:
       pb, _, mean, rstd = self.ln_pre.fwd(x_in, T, pd)
       ctx["ln_pre"] = (x_in, mean, rstd)
@@ -131,47 +129,16 @@ class NaflexExec:
     xL, saved = self.enc.fwd(x, n, N, save, enc_out, kv_len=lens)
     if collect:
       out["encoder"] = enc_out
-    ctx.update(pb=pb, W=W, enc=saved, xL=xL)
-    if m.pool_type == "map":
-      y, _, mean, rstd = self.enc.norm.fwd(xL, T, D)
-      z, msaved = self.map.fwd(y, n, N, kv_len=lens)
-      ctx.update(norm=(mean, rstd), map=msaved)
-      if collect:
-        out["encoded"] = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)[1].view(n, N, D)
-    elif m.pool_type == "gap":
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z = ops.pool_gap_fwd(yf, n, N, D, lens=lens)
-      ctx.update(norm=(mean, rstd))
-      if collect:
-        out["encoded"] = yf.view(n, N, D)
-    elif m.pool_type == "max":        # naflex_vit.py:267-271: padded tokens never win the maximum
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z, argmax = ops.pool_max_fwd(yf, n, N, D, lens=lens)
-      ctx.update(norm=(mean, rstd), argmax=argmax)
-      if collect:
-        out["encoded"] = yf.view(n, N, D)
-    elif m.pool_type == "none":
-      if save:
-        raise NotImplementedError("pool_type='none' is forward-only on the accelerated path")
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z = yf
-      if collect:
-        out["encoded"] = yf.view(n, N, D)
-    else:
-      raise NotImplementedError(f"pool_type '{m.pool_type}' (naflex_vit.py:267-271) is not implemented")
-    out["head_input"] = z.view(n, N, D) if m.pool_type == "none" else z      # (naflex_vit.py:276: set for every pool_type)
-    if self.pre is not None:
-      zb0 = ops.cast_bf16(z)
-      z = ops.tanh_fwd(E.linear_fwd(zb0, self.pre[0], self.pre[1], out_dtype=F32))
-      ctx["pre"] = (zb0, z)
+    # encoder_norm -> pooling over the valid tokens (naflex_vit.py:267-271: padded tokens never win the maximum) ->
+    # pre_logits -> head; pool_type "none": on every token, forward only
+    x, t_out, tctx = self.tail.fwd(xL, saved, n, N, kv_len=lens, want_encoded=collect)
+    ctx.update(pb=pb, W=W, tail=tctx)
+    if collect:
+      out["encoded"] = t_out["encoded"].view(n, N, D)
     per_token = (lambda t: t.view(n, N, -1)) if m.pool_type == "none" else (lambda t: t)     # [n, N, .] like the reference's
-    out["pre_logits"] = per_token(z)
-    x = z
-    if self.head is not None:
-      zb = ops.cast_bf16(z)
-      x = E.linear_fwd(zb, self.head[0], self.head[1], out_dtype=F32)
-      out["logits"] = per_token(x)
-      ctx["head_in"] = zb
+    for k in ("head_input", "pre_logits", "logits"):      # (naflex_vit.py:276: head_input is set for every pool_type)
+      if k in t_out:
+        out[k] = per_token(t_out[k])
     x = per_token(x)
     if perm is not None and collect:   # per-token diagnostics back in the caller's token order
       inv = torch.argsort(perm, dim=1)
@@ -186,36 +153,13 @@ class NaflexExec:
     return x, out, (ctx if save else None)
 
   def bwd(self, ctx, dx, on_block=None):
-    m = self.m
-    D = m.width
-    n, N, lens = ctx["n"], ctx["N"], ctx["lens"]
-    T = n * N
-    dz = dx.contiguous()
-    if self.head is not None:
-      dzb = ops.cast_bf16(dz)
-      E.linear_bwd_w(ctx["head_in"], dzb, self.head[0], self.head[1], dy_for_bias=dz)
-      dz = E.linear_bwd_x(dzb, self.head[0], out_dtype=F32)
-    if self.pre is not None:
-      zb0, y = ctx["pre"]
-      dpl = ops.tanh_bwd(y, dz.contiguous())
-      dplb = ops.cast_bf16(dpl)
-      E.linear_bwd_w(zb0, dplb, self.pre[0], self.pre[1], dy_for_bias=dpl)
-      dz = E.linear_bwd_x(dplb, self.pre[0], out_dtype=F32)
-    mean, rstd = ctx["norm"]
-    xL = ctx["xL"]
-    dxL_bf = torch.empty((T, D), device=xL.device, dtype=BF16)
-    if m.pool_type == "map":
-      dy = self.map.bwd(ctx["map"], dz, n, N)          # works from the saved (masked) probabilities
-      dxL = self.enc.norm.bwd(dy, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad())
-    else:
-      dyf = ops.pool_max_bwd(dz, ctx["argmax"], n, N, D) if m.pool_type == "max" else ops.pool_gap_bwd(dz, n, N, D, lens=lens)
-      dxL = self.enc.norm.bwd(dyf, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad())
-    dx0, dx0_bf = self.enc.bwd(ctx["enc"], dxL, dxL_bf, n, N, b2_done=True, on_block=on_block, kv_len=lens)
+    D, T = self.m.width, ctx["n"] * ctx["N"]
+    dx0, dx0_bf = self.tail.bwd(ctx["tail"], dx, on_block=on_block)
     # x = stem (+ patchln_post) + W . pos : d pos = W^T d x
     E.linear_bwd_w(ctx["W"], dx0_bf, self.pos, None)
     if self.ln_post is not None:
       t0, mean, rstd = ctx["ln_post"]
-      dt0_bf = torch.empty((T, D), device=xL.device, dtype=BF16)
+      dt0_bf = torch.empty((T, D), device=dx0.device, dtype=BF16)
       dt0 = self.ln_post.bwd(dx0, t0, mean, rstd, T, D, dx_bf16=dt0_bf)
     else:
       dt0, dt0_bf = dx0, dx0_bf

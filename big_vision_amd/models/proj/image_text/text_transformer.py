@@ -29,10 +29,10 @@ class TextExec:
     self.table = E._W(store, f"{prefix}Embed_0/embedding")
     self.pos = E._W(store, f"{prefix}pos_embedding", (seq_len, D))
     self.enc = E.Encoder(store, f"{prefix}Encoder_0", m.depth, D, H, M, scan=getattr(m, "scan", False))
-    self.map = E.MAPHead(store, f"{prefix}MAPHead_0", D, H, M) if m.pool_type == "map" else None
-    self.head = None
-    if m.num_classes:
-      self.head = (E._W(store, f"{prefix}head/kernel"), E._W(store, f"{prefix}head/bias"))
+    pool = {"last": "row", "first": "row", "mean": "gap", "gmp": "max"}.get(m.pool_type, m.pool_type)   # text_transformer.py:82-96
+    # (the selected token's encoder_norm also writes the head's bf16 operand)
+    self.tail = E.PooledTail(store, prefix, self.enc, pool, H, M, num_classes=m.num_classes,
+                             row=-1 if m.pool_type == "last" else 0, row_bf16=True)
 
   def fwd(self, text, save=False, collect=False, drop=None):
     """drop (engine.Dropout): train mode with dropout > 0 - the encoder blocks' sites (text_transformer.py:72-75)."""
@@ -47,9 +47,7 @@ class TextExec:
     xL, saved = self.enc.fwd(x, n, L, save, enc_out, drop=drop)
     if collect:
       out.update(enc_out)
-    ctx = dict(n=n, L=L, ids=ids, enc=saved, xL=xL)
-    T = n * L
-    if collect:
+      T = n * L
       _, yf, _, _ = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
       out["transformed"] = yf.view(n, L, D)
       # text_transformer.py:64 / :80: the token embedding before the position embedding, and the
@@ -59,63 +57,14 @@ class TextExec:
       vl = torch.empty((T, V), device=yf.device, dtype=F32)
       ops.sgemm(yf, D, 1, self.table.f32, 1, D, vl, T, V, D)
       out["vocab_logits"] = vl.view(n, L, V)
-    if m.pool_type in ("last", "first"):
-      off = L - 1 if m.pool_type == "last" else 0
-      zb, z, mean, rstd = self.enc.norm.fwd(xL, n, D, row_stride=L, row_offset=off, want_f32=True)
-      ctx.update(norm=(mean, rstd), off=off)
-    elif m.pool_type in ("mean", "gap"):
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z = ops.pool_gap_fwd(yf, n, L, D)
-      zb = ops.cast_bf16(z)
-      ctx.update(norm=(mean, rstd))
-    elif m.pool_type in ("max", "gmp"):       # text_transformer.py:89-90
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z, arg = ops.pool_max_fwd(yf, n, L, D)
-      zb = ops.cast_bf16(z)
-      ctx.update(norm=(mean, rstd), argmax=arg)
-    elif m.pool_type == "map":
-      y, _, mean, rstd = self.enc.norm.fwd(xL, T, D)
-      z, msaved = self.map.fwd(y, n, L)
-      zb = ops.cast_bf16(z)
-      ctx.update(norm=(mean, rstd), map=msaved)
-    else:
-      raise NotImplementedError(f"Cannot do pooling '{m.pool_type}'")
-    out["pre_logits"] = z
-    x = z
-    if self.head is not None:
-      x = E.linear_fwd(zb, self.head[0], self.head[1], out_dtype=F32)
-      out["logits"] = x
-      ctx["head_in"] = zb
+    x, t_out, tctx = self.tail.fwd(xL, saved, n, L)
+    out.update({k: t_out[k] for k in ("pre_logits", "logits") if k in t_out})
+    ctx = dict(n=n, L=L, ids=ids, tail=tctx)
     return x, out, (ctx if save else None)
 
   def bwd(self, ctx, dx, on_block=None):
-    m = self.m
-    D = m.width
-    n, L = ctx["n"], ctx["L"]
-    T = n * L
-    dz = dx.contiguous()
-    if self.head is not None:
-      dzb = ops.cast_bf16(dz)
-      E.linear_bwd_w(ctx["head_in"], dzb, self.head[0], self.head[1], dy_for_bias=dz)
-      dz = E.linear_bwd_x(dzb, self.head[0], out_dtype=F32)
-    mean, rstd = ctx["norm"]
-    xL = ctx["xL"]
-    dxL_bf = torch.empty((T, D), device=xL.device, dtype=BF16)
-    if m.pool_type in ("last", "first"):
-      dxL = torch.zeros((T, D), device=xL.device, dtype=F32)
-      dxL_bf.zero_()
-      self.enc.norm.bwd(dz, xL, mean, rstd, n, D, dx=dxL, dx_bf16=dxL_bf, row_stride=L, row_offset=ctx["off"],
-                        dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    elif m.pool_type in ("mean", "gap"):
-      dyf = ops.pool_gap_bwd(dz, n, L, D)
-      dxL = self.enc.norm.bwd(dyf, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    elif m.pool_type in ("max", "gmp"):
-      dyf = ops.pool_max_bwd(dz, ctx["argmax"], n, L, D)
-      dxL = self.enc.norm.bwd(dyf, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    else:
-      dy = self.map.bwd(ctx["map"], dz, n, L)
-      dxL = self.enc.norm.bwd(dy, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    dx0, _ = self.enc.bwd(ctx["enc"], dxL, dxL_bf, n, L, b2_done=not self.enc.dropped(ctx["enc"]), on_block=on_block)
+    n, L, D = ctx["n"], ctx["L"], self.m.width
+    dx0, _ = self.tail.bwd(ctx["tail"], dx, on_block=on_block)
     if self.table.grad is not None:
       ops.embed_bwd(ctx["ids"].view(-1), dx0, self.table.grad)
     if self.pos.grad is not None:

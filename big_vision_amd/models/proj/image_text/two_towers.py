@@ -109,6 +109,7 @@ class TwoTowersExec:
   def fwd(self, image, text, save=False, collect=False, drop_key=None):
     out, ctx = {}, {}
     zimg = ztxt = None
+    save = E.ctx_kind(save)
     save_img = save if self._tower_trainable("img/") else False
     save_txt = save if self._tower_trainable("txt/") else False
     tkw = self._drop_kw(self.m.text_tower, "txt", drop_key)

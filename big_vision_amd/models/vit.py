@@ -90,13 +90,8 @@ class VitExec:
       self.pos_const = torch.from_numpy(posemb_sincos_2d(hw[0], hw[1], D)[0]).to(store.device)
     self.cls = E._W(store, f"{prefix}cls", (1, D)) if m.pool_type == "tok" else None
     self.enc = E.Encoder(store, f"{prefix}Transformer", m.depth, D, H, M, scan=getattr(m, "scan", False))
-    self.map = E.MAPHead(store, f"{prefix}MAPHead_0", D, H, M) if m.pool_type == "map" else None
-    self.pre = None
-    if m.rep_size:   # pre_logits = tanh(Dense(x)), vit.py:259-262
-      self.pre = (E._W(store, f"{prefix}pre_logits/kernel"), E._W(store, f"{prefix}pre_logits/bias"))
-    self.head = None
-    if m.num_classes:
-      self.head = (E._W(store, f"{prefix}head/kernel"), E._W(store, f"{prefix}head/bias"))
+    self.tail = E.PooledTail(store, prefix, self.enc, "row" if m.pool_type in ("0", "tok") else m.pool_type, H, M,
+                             rep_size=m.rep_size, num_classes=m.num_classes, row=0)
 
   # -------------------------------------------------------------- forward --
   def fwd(self, image, save=False, collect=False, drop=None):
@@ -132,101 +127,35 @@ class VitExec:
     xL, saved = self.enc.fwd(x, n, L, save, enc_out, drop=drop)
     if collect:
       out["encoder"] = enc_out
-    ctx = dict(n=n, L=L, L0=L0, patches=patches, enc=saved, xL=xL, k_pos=k_pos)
-    T = n * L
-    if m.pool_type == "map":
-      y, _, mean, rstd = self.enc.norm.fwd(xL, T, D)
-      z, msaved = self.map.fwd(y, n, L)
-      ctx.update(norm=(mean, rstd), map=msaved)
-      if collect:
-        out["encoded"] = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)[1].view(n, L, D)
-    elif m.pool_type == "gap":
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z = ops.pool_gap_fwd(yf, n, L, D)
-      ctx.update(norm=(mean, rstd))
-      if collect:
-        out["encoded"] = yf.view(n, L, D)
-    elif m.pool_type in ("0", "tok"):
-      if collect:
-        _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-        enc = yf.view(n, L, D)
-        out["encoded"] = enc   # all L (+1 cls) tokens, as in the reference (vit.py:240); x_2d drops the cls row
-        z = enc[:, 0].contiguous()
-        mean, rstd = mean.view(n, L)[:, 0].contiguous(), rstd.view(n, L)[:, 0].contiguous()
-      else:
-        _, z, mean, rstd = self.enc.norm.fwd(xL, n, D, row_stride=L, row_offset=0, want_bf16=False, want_f32=True)
-      ctx.update(norm=(mean, rstd))
-    elif m.pool_type == "none":
-      # vit.py:252-253: no pooling, the tail (pre_logits / head) runs on every token; forward only
-      # (no trainer on the accelerated path back-propagates through an un-pooled tower)
-      if save:
-        raise NotImplementedError("pool_type='none' is forward-only on the accelerated path")
-      _, yf, mean, rstd = self.enc.norm.fwd(xL, T, D, want_bf16=False, want_f32=True)
-      z = yf
-      if collect:
-        out["encoded"] = yf.view(n, L, D)
-    else:
-      raise ValueError(f"Unknown pool type: '{m.pool_type}'")
+    # encoder_norm -> pooling -> pre_logits -> head; with pool_type "none" (vit.py:252-253) on every token, forward only
+    # (no trainer on the accelerated path back-propagates through an un-pooled tower)
+    x, t_out, tctx = self.tail.fwd(xL, saved, n, L, want_encoded=collect)
+    ctx = dict(n=n, L=L, L0=L0, patches=patches, tail=tctx, k_pos=k_pos)
+    if collect:
+      out["encoded"] = t_out["encoded"].view(n, L, D)   # all L (+1 cls) tokens, as in the reference (vit.py:240); x_2d drops the cls row
+    per_token = (lambda t: t.view(n, L, -1)) if m.pool_type == "none" else (lambda t: t)   # like the reference's un-pooled x
     if m.pool_type != "none":
-      out["head_input"] = z
-    if self.pre is not None:
-      zb0 = ops.cast_bf16(z)
-      z = ops.tanh_fwd(E.linear_fwd(zb0, self.pre[0], self.pre[1], out_dtype=F32))
-      ctx["pre"] = (zb0, z)
-    out["pre_logits"] = z
-    x = z
-    if self.head is not None:
-      zb = ops.cast_bf16(z)
-      x = E.linear_fwd(zb, self.head[0], self.head[1], out_dtype=F32)
-      out["logits"] = x
-      ctx["head_in"] = zb
-    if m.pool_type == "none":   # [n, L, features], like the reference's un-pooled x
-      for k in ("pre_logits", "logits"):
-        if k in out:
-          out[k] = out[k].view(n, L, -1)
-      x = x.view(n, L, -1)
+      out["head_input"] = t_out["head_input"]
+    for k in ("pre_logits", "logits"):
+      if k in t_out:
+        out[k] = per_token(t_out[k])
+    x = per_token(x)
+    pre, head = self.tail.pre, self.tail.head
     if collect and "encoded" in out:
       # the same tail applied to every patch token (vit.py:257-273: x_2d; unused by training)
       x2 = (out["encoded"][:, 1:] if m.pool_type == "tok" else out["encoded"]).contiguous().view(n * L0, D)
-      if self.pre is not None:
-        x2 = ops.tanh_fwd(E.linear_fwd(ops.cast_bf16(x2), self.pre[0], self.pre[1], out_dtype=F32))
+      if pre is not None:
+        x2 = ops.tanh_fwd(pre.fwd(ops.cast_bf16(x2)))
       out["pre_logits_2d"] = x2.view(n, h, w, -1)
-      if self.head is not None:
-        out["logits_2d"] = E.linear_fwd(ops.cast_bf16(x2), self.head[0], self.head[1], out_dtype=F32).view(n, h, w, -1)
+      if head is not None:
+        out["logits_2d"] = head.fwd(ops.cast_bf16(x2)).view(n, h, w, -1)
     return x, out, (ctx if save else None)
 
   # ------------------------------------------------------------- backward --
   def bwd(self, ctx, dx, on_block=None):
-    m = self.m
-    D = m.width
+    m, D = self.m, self.m.width
     n, L, L0 = ctx["n"], ctx["L"], ctx["L0"]
-    T = n * L
-    dz = dx.contiguous()
-    if self.head is not None:
-      dzb = ops.cast_bf16(dz)
-      E.linear_bwd_w(ctx["head_in"], dzb, self.head[0], self.head[1], dy_for_bias=dz)
-      dz = E.linear_bwd_x(dzb, self.head[0], out_dtype=F32)
-    if self.pre is not None:
-      zb0, y = ctx["pre"]
-      dpl = ops.tanh_bwd(y, dz.contiguous())
-      dplb = ops.cast_bf16(dpl)
-      E.linear_bwd_w(zb0, dplb, self.pre[0], self.pre[1], dy_for_bias=dpl)
-      dz = E.linear_bwd_x(dplb, self.pre[0], out_dtype=F32)
-    mean, rstd = ctx["norm"]
-    xL = ctx["xL"]
-    dxL_bf = torch.empty((T, D), device=xL.device, dtype=BF16)
-    if m.pool_type == "map":
-      dy = self.map.bwd(ctx["map"], dz, n, L)
-      dxL = self.enc.norm.bwd(dy, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    elif m.pool_type == "gap":
-      dyf = ops.pool_gap_bwd(dz, n, L, D)
-      dxL = self.enc.norm.bwd(dyf, xL, mean, rstd, T, D, dx_bf16=dxL_bf, dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    else:
-      dxL = torch.zeros((T, D), device=xL.device, dtype=F32)
-      dxL_bf.zero_()
-      self.enc.norm.bwd(dz, xL, mean, rstd, n, D, dx=dxL, dx_bf16=dxL_bf, row_stride=L, row_offset=0,
-                        dx_colsum=self.enc.last_b2_grad(ctx["enc"]))
-    dx0, dx0_bf = self.enc.bwd(ctx["enc"], dxL, dxL_bf, n, L, b2_done=not self.enc.dropped(ctx["enc"]), on_block=on_block)
+    dx0, dx0_bf = self.tail.bwd(ctx["tail"], dx, on_block=on_block)
     if ctx.get("k_pos") is not None:    # backward of the dropout behind the position embedding: the same keep bits
       ops.dropout_f32(dx0, ctx["k_pos"][1], ctx["k_pos"][0], out=dx0, out_bf16=dx0_bf)
     if m.pool_type == "tok":

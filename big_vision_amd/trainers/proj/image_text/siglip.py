@@ -109,6 +109,8 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
   if comm.active and config.get("overlap_grad_sync", True):
     dp.warn_if_overlap_is_uncapped()   # the persistent GEMMs leave dp.RESERVED_CUS CUs to RCCL: cap its channels
 
+  light_of = lambda kind: False if kind == E.FULL else kind     # a context kind in state_cache["light"]'s spelling
+
   towers_drop = any(float(getattr(t, "dropout", 0.0) or 0.0) > 0.0
                     for t in (getattr(model, "image_tower", None), getattr(model, "text_tower", None)))
 
@@ -155,7 +157,7 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
       # so every tower backward has to wait for all embeddings.  The activations of as many
       # micro-batches as fit in HBM (288 GB on MI355X) are KEPT; only the rest is recomputed
       # in pass 2 (a pure memory/compute trade: results are identical either way).  When the
-      # full contexts do not all fit, "light" contexts are kept instead (engine.Block.fwd:
+      # full contexts do not all fit, lighter kinds are kept instead (engine.ctx_kind, engine.Block.fwd:
       # LayerNorm outputs and gelu(h) are re-derived by the backward, 1/3 fewer bytes).
       starts = list(range(0, n, micro))
       dev = labels.device
@@ -172,19 +174,18 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
       def fits(per_ctx, count):
         return headroom() - margin >= count * (per_ctx + per_ctx // 32)
 
-      # state_cache["light"]: None = undecided ("auto", first step), False = full contexts, "g" = contexts
-      # without gelu(h) (re-emitted by the fc2 dX GEMM), True / "light" = also without the LayerNorm outputs
-      if state_cache["light"] is None:
-        state_cache["light"] = ({"g": "g", "light": "light"}.get(light_cfg, bool(light_cfg))
-                                if light_cfg != "auto" else None)
-      mode_of = lambda l: "light" if l in (True, "light") else ("g" if l == "g" else True)
+      # state_cache["light"] (read by bench.py and the tests; microbatch_light's own spelling): None = undecided
+      # ("auto", first step), False = engine.FULL contexts, otherwise the kind (engine.NO_GELU: without gelu(h), re-emitted by
+      # the fc2 dX GEMM; engine.LIGHT - or True when the config said True: also without the LayerNorm outputs)
+      if state_cache["light"] is None and light_cfg != "auto":
+        state_cache["light"] = light_cfg if light_cfg is True else light_of(E.ctx_kind(light_cfg, light_flag=True))
       zi, zt, kept, norms = [], [], {}, []
       for k, s in enumerate(starts):
-        mode = mode_of(state_cache["light"])
+        mode = E.ctx_kind(state_cache["light"], light_flag=True)
         per_ctx = state_cache["per_ctx"].get(mode)
         keep = len(kept) < keep_max and (per_ctx is None or keep_cfg == "all" or fits(per_ctx, 1))
         before = torch.cuda.memory_allocated(dev)
-        a, b, o_, c = ex.fwd(_img_slice(images, s, s + micro), labels[s:s + micro], save=(mode if keep else False),
+        a, b, o_, c = ex.fwd(_img_slice(images, s, s + micro), labels[s:s + micro], save=(mode if keep else None),
                              drop_key=drop_key(s))
         norms.append((o_.get("img/norm"), o_.get("txt/norm")))
         if keep and per_ctx is None:
@@ -194,11 +195,12 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
             # without gelu(h), then light (each trial re-runs this micro-batch's forward once)
             others = min(keep_max, len(starts)) - 1
             state_cache["light"] = False
-            for trial in ("g", "light"):
+            for trial in (E.NO_GELU, E.LIGHT):
               if keep_max <= 1 or fits(per_ctx, others):
                 break
               del c
-              state_cache["light"] = mode = trial
+              mode = trial
+              state_cache["light"] = light_of(mode)
               before = torch.cuda.memory_allocated(dev)
               a, b, _, c = ex.fwd(_img_slice(images, s, s + micro), labels[s:s + micro], save=mode, drop_key=drop_key(s))
               per_ctx = state_cache["per_ctx"][mode] = max(1, torch.cuda.memory_allocated(dev) - before)
@@ -216,7 +218,7 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
         ctx = kept.pop(s, None)
         if ctx is None:
           _, _, _, ctx = ex.fwd(_img_slice(images, s, s + micro), labels[s:s + micro],
-                                save=mode_of(state_cache["light"]), drop_key=drop_key(s))
+                                save=E.ctx_kind(state_cache["light"], light_flag=True), drop_key=drop_key(s))
         with dp.reserve_cus_for_collectives(comm if (sync is not None and s == starts[-1]) else None):
           ex.bwd(ctx, None if img_frozen else dzimg[s:s + micro].contiguous(),
                  None if txt_frozen else dztxt[s:s + micro].contiguous(),
@@ -224,10 +226,9 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
         del ctx
     else:
       # one pass over the whole per-device batch; config.microbatch_light also applies here (the same context kinds
-      # as the two-pass path: True / "light" = LayerNorm outputs and gelu(h) re-derived by the backward, "g" =
-      # gelu(h) only) - a memory knob that changes no result
+      # as the two-pass path; "auto" = full contexts) - a memory knob that changes no result
       light_cfg = config.get("microbatch_light", "auto")
-      save = "light" if light_cfg in (True, "light") else ("g" if light_cfg == "g" else True)
+      save = E.FULL if light_cfg == "auto" else E.ctx_kind(light_cfg, light_flag=True)
       zimg, ztxt, o_, ctx = ex.fwd(images, labels, save=save, drop_key=drop_key(0))
       norms = [(o_.get("img/norm"), o_.get("txt/norm"))]
       stats, dzimg, dztxt, *lx = loss_fwd_bwd(zimg, ztxt, t_param, b_param, comm)

@@ -280,8 +280,11 @@ def attn_fwd(qkv, n, L, H, kv_len=None):
   return o, lse
 
 
-def attn_bwd(qkv, o, d_o, lse, n, L, H, dqkv=None, dbias=None, kv_len=None):
-  """dbias (fp32, 3*H*Dh elements): += column sums of dqkv (the q/k/v bias gradients)."""
+def attn_bwd(qkv, o, d_o, lse, n, L, H, dqkv=None, dbias=None, kv_len=None, delta=None):
+  """dbias (fp32, 3*H*Dh elements): += column sums of dqkv (the q/k/v bias gradients).
+  delta (fp32 [n, H, L], optional): the caller's buffer for the kernels' rowsum(P o dP) scratch, so that tests can
+  read it back; the one-launch backward (unmasked Dh = 64, L <= 64 or 193..208) keeps it in LDS and leaves the
+  buffer untouched."""
   _chk(qkv, BF16, "attn.qkv"); _chk(o, BF16, "attn.o"); _chk(d_o, BF16, "attn.do")
   assert d_o.is_contiguous() and o.is_contiguous()
   Dh = _head_dim(qkv.numel(), n * L, 3, H, "attn_bwd")
@@ -290,7 +293,11 @@ def attn_bwd(qkv, o, d_o, lse, n, L, H, dqkv=None, dbias=None, kv_len=None):
   if dbias is not None:
     _chk(dbias, F32, "attn.dbias")
     assert dbias.is_contiguous() and dbias.numel() == 3 * H * Dh
-  delta = torch.empty((n, H, L), device=qkv.device, dtype=F32)
+  if delta is None:
+    delta = torch.empty((n, H, L), device=qkv.device, dtype=F32)
+  else:
+    _chk(delta, F32, "attn.delta")
+    assert delta.is_contiguous() and delta.shape == (n, H, L)
   rows = torch.empty((n, 3 * H * Dh), device=qkv.device, dtype=F32) if dbias is not None else None
   if kv_len is not None:
     _chk(kv_len, torch.int32, "attn.kv_len")

@@ -23,6 +23,7 @@ Every checker takes the assertion's previous `(rtol, atol)` as `legacy=`: the bo
 what share of the elements the legacy cap (not the model) applies.  NaN / Inf in an output fail (the old
 `err > tol` test let a NaN through: every comparison with NaN is false).
 """
+import collections
 import math
 
 import torch
@@ -377,6 +378,216 @@ def attn_fwd_bounds(qkv, n, L, H, Dh, lens=None):
   return o_ref, o_b, lse, f32_bound(lse, e_lse)
 
 
+# --------------------------------------------------- attention backward ----
+# What the kernels document (headers and comments of attention3.hip, attention5.hip, attention_dh.hip), per path:
+#   every path   S and dP fp32-accumulated over Dh; P = exp2(S c - lse log2 e) from the STORED fp32 lse (so P carries
+#                the forward's lse error); dS = P o (dP - delta) in fp32; dV takes bf16(P), dQ / dK take bf16(dS) as
+#                MFMA operands, accumulated over L in fp32; 1 / sqrt(Dh) (0.125 exactly at Dh = 64, the fp32
+#                1 / sqrtf(Dh) otherwise) multiplies the fp32 accumulator; one round-to-nearest-even to bf16.  Masked
+#                (key-padded) launches take the same arithmetic: P of a padded key is exactly 0, so are its dK / dV.
+#   attn3 dq     (masked Dh = 64; every adh launch) two sweeps: delta = fp32 rowsum(P o dP), stored.
+#   attn3 dq1    (unmasked Dh = 64 outside the one-launch shapes) one sweep: delta~ = rowsum(dO o bf16 O),
+#                dS~ = P o (dP - delta~), eps = rowsum(dS~), dQ = sum bf16(dS~) K - eps sum bf16(P) K, delta = delta~
+#                + eps is stored for the dK / dV launch.  In exact arithmetic that is P o (dP - delta) with delta =
+#                rowsum(P o dP) + delta~ (1 - rowsum P): the terms below marked "dq1".
+#   attn5        (unmasked Dh = 64, L <= 64 or 193..208) one launch: delta as attn3 dq but kept in LDS (never
+#                stored: the delta buffer is NOT filled on this path); phase 1b forms dS from the bf16 P of the LDS
+#                image, so dS carries one more 2^-8 rounding: the terms marked "attn5".
+#   bias rows    every path sums the fp32 accumulators (after the scale, BEFORE the bf16 rounding) over a (sample,
+#                head)'s rows - DPP row sums + per-wave LDS rows (attention3 / attention5 BM = 1, 3), fp32 atomics
+#                (attention_dh) - and ops.attn_bwd sums the per-sample rows (bv_colsum).  attention5 uses identities
+#                where it can: v-bias = column sums of dO, k-bias = exactly 0, and for L % 16 != 0 (BM = 2) q-bias =
+#                scale sum_key bf16(cs_key) K[key], cs_key = fp32 sum_q bf16(dS[q][key]).
+#
+# Headroom (worst max err / bound).  fp32 emulation of the documented arithmetic on the CPU
+# (tests/test_tolerance_power_cpu.py, n = 2, H = 2, qkv seed 1 x 1.5, dO seed 2):
+#   family (L, Dh)              dq    dk    dv    delta  dbias q / k / v    model / legacy tolerance, median (max)
+#   attn3 dq+dkv (64, 64)       0.74  0.75  0.81  <0.01  0.18 0.17 0.19     0.024 (0.12)
+#   attn5        (64, 64)       0.71  0.62  0.81  <0.01  0.15 0.13 0.19     0.035 (0.22)
+#   attn3 dq+dkv (197, 64)      0.75  0.75  0.80  <0.01  0.10 0.11 0.20     0.023 (0.14)
+#   attn5        (197, 64)      0.73  0.63  0.80  <0.01  0.07 0.15 0.20     0.037 (0.24)
+#   attn3 dq+dkv (441, 64)      0.70  0.72  0.74  <0.01  0.09 0.09 0.15     0.021 (0.15)
+#   dq1 + dkv32  (441, 64)      0.70  0.71  0.74  <0.01  0.06 0.08 0.15     0.021 (0.15)
+#   adh          (100, 72)      0.79  0.77  0.84  <0.01  0.16 0.14 0.17     0.023 (0.14)
+# The MI355X figures per kernel family are printed by every check ("[bounds] <case> [<family>] <part>: max err/bound")
+# when the GPU files run with -s; they were not measured when this section was written (no GPU was available) and a
+# value above 1 there is a failure to explain from the kernel source, not a number to absorb.
+AttnBwd = collections.namedtuple("AttnBwd", "g g_bound delta delta_bound db db_bound path")
+NO_LEGACY = (0.0, float("inf"))   # for outputs that no earlier assertion covered (delta)
+
+
+def attn_bwd_path(L, Dh, masked, one_launch=True):
+  """The kernel family ops.attn_bwd dispatches to (attention.hip / attention3.hip bv_attn3_bwd)."""
+  if Dh != 64 or L > 576:
+    return "adh"
+  if masked:
+    return "attn3 dq+dkv"
+  if one_launch and (L <= 64 or 192 < L <= 208):
+    return "attn5"
+  return "attn3 dq1+dkv" if L <= 272 else "attn3 dq1+attn4 dkv32"
+
+
+def _attn_bwd_chunk(qkv, d_o, m, L, H, Dh, lens, path):
+  q, k, v = qkv.double().view(m, L, 3, H, Dh).unbind(2)
+  do = d_o.double().view(m, L, H, Dh)
+  sc = 1.0 / math.sqrt(Dh)
+  o_ref, o_b, lse, lse_b = attn_fwd_bounds(qkv, m, L, H, Dh, lens)
+  s = torch.einsum("nqhd,nkhd->nhqk", q, k) * sc
+  es = torch.einsum("nqhd,nkhd->nhqk", q.abs(), k.abs()) * sc * gamma(Dh) * U   # fp32 accumulation of S over Dh
+  if lens is not None:
+    mask = torch.arange(L, device=s.device)[None, :] < torch.as_tensor(lens, device=s.device)[:, None]
+    s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
+  p = torch.exp(s - lse[..., None])
+  sabs = s.abs().nan_to_num(0.0, posinf=0.0, neginf=0.0)
+  # relative error of P: the S accumulation, the stored lse (within the forward's lse bound), the fp32 exponent
+  # argument fma(S, c, -lse log2 e) and the hardware exp2
+  rel_p = es + lse_b[..., None] + 8 * U * (sabs + lse.abs()[..., None] + 1)
+  dp = torch.einsum("nqhd,nkhd->nhqk", do, v)
+  e_dp = gamma(Dh) * U * torch.einsum("nqhd,nkhd->nhqk", do.abs(), v.abs())          # fp32 accumulation of dP over Dh
+  delta = (p * dp).sum(-1)
+  e_delta = (p * (e_dp + rel_p * dp.abs())).sum(-1)                                  # P and dP errors carried into the row sum
+  e_delta = e_delta + (gamma(L) + 2) * U * (p * dp.abs()).sum(-1)                    # fp32 row sum over L (+ the product)
+  epsb = 0.0
+  if "dq1" in path:
+    # dq1: |delta - delta~| <= sum_d |dO| |O_kernel - O| (the forward's o bound) + the fp32 dot product over Dh
+    o_err = o_b.view(m, L, H, Dh) + gamma(Dh) * U * o_ref.abs().view(m, L, H, Dh)
+    epsb = (do.abs() * o_err).sum(-1).permute(0, 2, 1)
+    # dq1: the stored delta is rowsum(P o dP) + delta~ (1 - rowsum P); rowsum P is 1 only to the relative error of P
+    e_delta = e_delta + (delta.abs() + epsb) * ((p * rel_p).sum(-1) + (gamma(L) + 4) * U)
+    epsb = epsb[..., None]
+  ds = p * (dp - delta[..., None])
+  e_ds = p * (e_dp + e_delta[..., None]) + (rel_p + 2 * U) * ds.abs()                # dP, delta, P errors + the 2 fp32 ops
+  # Operand roundings, exactly: one round-to-nearest-even of x to bf16 is off by at most half a bf16 ulp AT x (between
+  # 2^-9 |x| and 2^-8 |x|, by x's mantissa), the ulp taken at |x| + its own error as in bf16_bound.  A flat 2^-8 |x|
+  # is up to twice that and lets a second rounding of dP or delta hide inside the bound.
+  h_p = 0.5 * ulp_bf16(p * (1 + rel_p))                      # bf16(P)
+  # dq1: bf16 rounding of dS~ = dS + (delta - delta~) P, and of the bf16 P of the eps correction term
+  dsq = ds.abs() + epsb * p
+  if path == "attn5":
+    # attn5: dS = bf16(P) (dP - delta), then bf16(dS): the P rounding carried through the product + the dS rounding
+    via_p = h_p * (dp - delta[..., None]).abs()
+    a_k = via_p + 0.5 * ulp_bf16(ds.abs() + via_p + e_ds)
+    a_q = a_k
+  else:
+    a_k = 0.5 * ulp_bf16(ds.abs() + e_ds)
+    a_q = 0.5 * ulp_bf16(dsq + e_ds) + epsb * h_p            # (dq1: + eps times the rounding of the correction's bf16 P)
+  a_v = h_p
+  s_q = e_ds + gamma(L) * U * dsq                            # dS error + fp32 accumulation over L
+  s_k = e_ds + gamma(L) * U * ds.abs()
+  s_v = p * (rel_p + gamma(L) * U)                           # P error + fp32 accumulation over L
+  dq = torch.einsum("nhqk,nkhd->nqhd", ds, k) * sc
+  dk = torch.einsum("nhqk,nqhd->nkhd", ds, q) * sc
+  dv = torch.einsum("nhqk,nqhd->nkhd", p, do)
+  # + the scale multiply (and the rounding of 1 / sqrtf(Dh) itself for Dh != 64) on the fp32 accumulator
+  e_sys = torch.stack([torch.einsum("nhqk,nkhd->nqhd", s_q, k.abs()) * sc + 2 * U * dq.abs(),
+                       torch.einsum("nhqk,nqhd->nkhd", s_k, q.abs()) * sc + 2 * U * dk.abs(),
+                       torch.einsum("nhqk,nqhd->nkhd", s_v, do.abs())], 2).reshape(m * L, 3 * H * Dh)
+  e_rnd = torch.stack([torch.einsum("nhqk,nkhd->nqhd", a_q, k.abs()) * sc,
+                       torch.einsum("nhqk,nqhd->nkhd", a_k, q.abs()) * sc,
+                       torch.einsum("nhqk,nqhd->nkhd", a_v, do.abs())], 2).reshape(m * L, 3 * H * Dh)
+  g = torch.stack([dq, dk, dv], 2).reshape(m * L, 3 * H * Dh)
+  # Bias rows sum the fp32 accumulators of all rows.  Their systematic errors add up; the operand roundings are one
+  # independent round-to-nearest-even per (query, key) element, so over the rows x L terms of a column they add in
+  # quadrature (the module's probabilistic rule, LAM sqrt(sum of squares)) - the worst-case sum would exceed the
+  # column sum of |g| itself.
+  sys_db = e_sys.sum(0)
+  var_db = torch.stack([torch.einsum("nhqk,nkhd->hd", a_q ** 2, k ** 2) * sc ** 2,
+                        torch.einsum("nhqk,nqhd->hd", a_k ** 2, q ** 2) * sc ** 2,
+                        torch.einsum("nhqk,nqhd->hd", a_v ** 2, do ** 2)]).reshape(-1)
+  if path == "attn5" and L % 16:
+    # attn5 BM = 2: cs_key is rounded to bf16 before the K contraction that yields the q-bias gradient
+    cs = ds.sum(2)                                           # [m, H, L(key)]
+    sys_db[:H * Dh] += (U_BF16 * sc * torch.einsum("nhk,nkhd->nhd", cs.abs(), k.abs())).sum(0).reshape(-1)
+  return g, e_sys + e_rnd, delta, e_delta, sys_db, var_db
+
+
+def attn_bwd_bounds(qkv, d_o, n, L, H, Dh, lens=None, path=None, chunk_elems=1 << 22):
+  """Self-attention backward on the bf16 qkv [n L, 3 H Dh] and dO [n L, H Dh], fp64: AttnBwd(g, g_bound [n L, 3 H Dh]
+  (dq | dk | dv, bf16 outputs), delta, delta_bound [n, H, L] (fp32), db, db_bound [3 H Dh] (fp32 column sums of g,
+  bound without the caller's initial value), path).  path (attn_bwd_path) selects the documented variant terms; the
+  model runs over blocks of samples so that no [n, H, L, L] tensor exceeds chunk_elems."""
+  if path is None:
+    path = attn_bwd_path(L, Dh, lens is not None)
+  step = max(1, chunk_elems // (H * L * L))
+  gs, es, ds_, eds, edb, vdb = [], [], [], [], 0.0, 0.0
+  for i0 in range(0, n, step):
+    i1 = min(n, i0 + step)
+    g, e, d, ed, eb, vb = _attn_bwd_chunk(qkv[i0 * L:i1 * L], d_o[i0 * L:i1 * L], i1 - i0, L, H, Dh,
+                                      None if lens is None else list(lens[i0:i1]), path)
+    gs.append(g); es.append(bf16_bound(g, e)); ds_.append(d); eds.append(f32_bound(d, ed)); edb = edb + eb; vdb = vdb + vb
+  g = torch.cat(gs)
+  db = g.sum(0)
+  # + the fp32 summation over the n L rows (row sums, per-wave rows, per-sample rows, bv_colsum)
+  edb = edb + LAM * torch.sqrt(vdb) + gamma(n * L) * U * g.abs().sum(0)
+  return AttnBwd(g, torch.cat(es), torch.cat(ds_), torch.cat(eds), db, edb, path)
+
+
+def capped_share(ref, bound, legacy):
+  """Share of the elements on which the legacy tolerance, not the model, is the bound."""
+  return (~(bound.double() <= legacy[1] + legacy[0] * ref.double().abs())).double().mean().item()
+
+
+# --------------------------------------------------------- MAP attention ----
+# attention.hip map_attn_* (Dh = 64) and attention_dh.hip adh_map_*: one wave per (sample, head), everything fp32 on
+# the VALU (no bf16 operand): s = (q . k) scale accumulated over Dh, p = exp(s - max) / sum (stored fp32; keys >=
+# kv_len get p = 0 exactly), o = bf16(sum_l p v) accumulated over L; backward from the STORED p: dp = dO . v over
+# Dh, dsum = sum_l p dp (wave sum), ds = p (dp - dsum), dv = bf16(p dO), dk = bf16(ds (q scale)), dq = bf16(scale
+# sum_l ds k).
+MapAttn = collections.namedtuple("MapAttn", "p p_bound o o_bound dq dq_bound dkv dkv_bound")
+
+
+def _map_core(q, kv, n, L, H, Dh, lens):
+  qd = q.double().view(n, H, Dh)
+  k, v = kv.double().view(n, L, 2, H, Dh).unbind(2)
+  sc = 1.0 / math.sqrt(Dh)
+  s = torch.einsum("nhd,nkhd->nhk", qd, k) * sc
+  es = torch.einsum("nhd,nkhd->nhk", qd.abs(), k.abs()) * sc * gamma(Dh) * U          # fp32 accumulation of s over Dh
+  if lens is not None:
+    ln = torch.as_tensor(lens, device=s.device).long().clamp(1, L)
+    s = s.masked_fill(~(torch.arange(L, device=s.device)[None, :] < ln[:, None])[:, None, :], float("-inf"))
+  p = torch.softmax(s, -1)
+  sabs = s.abs().nan_to_num(0.0, posinf=0.0, neginf=0.0)
+  t = es + 8 * U * (sabs + s.amax(-1, keepdim=True).abs() + 1)    # s error, the fp32 exponent argument, the exp
+  t = torch.where(p > 0, t, torch.zeros_like(t))
+  # p = e / sum e: the element's own error, the sum's (at most the row maximum, + the wave sum over L), the divide
+  rel_p = t + t.amax(-1, keepdim=True) + (gamma(L) + 4) * U
+  return qd, k, v, sc, p, rel_p
+
+
+def map_attn_fwd_bounds(q, kv, n, L, H, Dh, lens=None):
+  """(p_ref [n, H, L], p bound (fp32 output), o_ref [n, H Dh], o bound (bf16 output)), fp64."""
+  qd, k, v, sc, p, rel_p = _map_core(q, kv, n, L, H, Dh, lens)
+  o = torch.einsum("nhk,nkhd->nhd", p, v)
+  e_o = torch.einsum("nhk,nkhd->nhd", p * (rel_p + gamma(L) * U), v.abs())            # p error + fp32 accumulation over L
+  return p, f32_bound(p, rel_p * p), o.reshape(n, H * Dh), bf16_bound(o, e_o).reshape(n, H * Dh)
+
+
+def map_attn_bwd_bounds(q, kv, d_o, n, L, H, Dh, lens=None):
+  """(dq_ref [n, H Dh], dq bound, dkv_ref [n L, 2 H Dh], dkv bound), bf16 outputs, fp64; the kernel's p is the
+  forward's stored one, within map_attn_fwd_bounds' p bound of the exact softmax the reference uses."""
+  qd, k, v, sc, p, rel_p = _map_core(q, kv, n, L, H, Dh, lens)
+  do = d_o.double().view(n, H, Dh)
+  rel_p = rel_p + F32_ULPS * U                                                        # the stored fp32 p
+  dp = torch.einsum("nhd,nkhd->nhk", do, v)
+  e_dp = gamma(Dh) * U * torch.einsum("nhd,nkhd->nhk", do.abs(), v.abs())             # fp32 accumulation of dp over Dh
+  dsum = (p * dp).sum(-1, keepdim=True)
+  e_dsum = (p * (e_dp + rel_p * dp.abs())).sum(-1, keepdim=True)                      # p and dp errors in the row sum
+  e_dsum = e_dsum + (gamma(L) + 2) * U * (p * dp.abs()).sum(-1, keepdim=True)         # fp32 (wave) sum over L
+  ds = p * (dp - dsum)
+  e_ds = p * (e_dp + e_dsum) + (rel_p + 2 * U) * ds.abs()                             # dp, dsum, p errors + the 2 fp32 ops
+  dq = torch.einsum("nhk,nkhd->nhd", ds, k) * sc
+  # ds error + fp32 accumulation over L + the scale multiply
+  e_dq = torch.einsum("nhk,nkhd->nhd", e_ds + gamma(L) * U * ds.abs(), k.abs()) * sc + 2 * U * dq.abs()
+  dk = ds.permute(0, 2, 1)[..., None] * qd[:, None] * sc
+  e_dk = e_ds.permute(0, 2, 1)[..., None] * qd.abs()[:, None] * sc + 4 * U * dk.abs() # ds error + (q scale), product
+  dv = p.permute(0, 2, 1)[..., None] * do[:, None]
+  e_dv = (rel_p.permute(0, 2, 1)[..., None] + 2 * U) * dv.abs()                       # p error + the product
+  dkv = torch.stack([dk, dv], 2).reshape(n * L, 2 * H * Dh)
+  e_dkv = torch.stack([e_dk, e_dv], 2).reshape(n * L, 2 * H * Dh)
+  return dq.reshape(n, H * Dh), bf16_bound(dq, e_dq).reshape(n, H * Dh), dkv, bf16_bound(dkv, e_dkv)
+
+
+
 # ------------------------------------------------- checkers of the GPU tests ----
 def check_gemm(out, ref, a, b_t, legacy, name, n_adds=1, alpha=1.0):
   """GEMM output (bf16 or fp32 by out's dtype) of A [M][K] @ B^T [K][N] (+ n_adds fp32 epilogue adds) vs the fp64 ref."""
@@ -425,6 +636,56 @@ def check_attn_fwd(o, lse, qkv, n, L, H, Dh, lens=None, legacy_o=(2e-2, 2e-2), l
   o_ref, ob, lse_ref, lb = attn_fwd_bounds(qkv, n, L, H, Dh, lens)
   check(lse, lse_ref, lb, legacy_lse, name + " lse")
   check(o, o_ref, ob, legacy_o, name + " out")
+
+
+def check_attn_bwd(dqkv, qkv, d_o, n, L, H, Dh, lens=None, legacy=3e-2, delta=None, dbias=None, dbias_base=0.0,
+                   legacy_db=2e-2, path=None, name="attn bwd", bounds=None):
+  """Self-attention backward outputs against attn_bwd_bounds.  legacy / legacy_db: the flat tolerances these
+  assertions had before, r meaning (rtol, atol) = (r, r max|ref|) with the maximum over the whole tensor (dqkv) /
+  over the column sums of |g| (dbias) - they cap the model bound.
+  delta: the buffer the backward entry point filled ([n, H, L] fp32), compared with fp64 rowsum(P o dP).  The "attn5"
+  path (attention5.hip, the one-launch backward) keeps its delta partials in LDS and does NOT fill the buffer: there,
+  and only there, a delta that is passed is not looked at.
+  dbias: the fp32 bias-gradient vector after the launch (dbias_base + column sums); the k-bias third is 0 in exact
+  arithmetic (the rows of dS sum to 0), so its bound is the model's alone - the legacy cap is far above it.
+  Returns {part: max err / bound}."""
+  b = attn_bwd_bounds(qkv, d_o, n, L, H, Dh, lens, path) if bounds is None else bounds
+  tag = f"{name} [{b.path}]"
+  leg = (legacy, legacy * b.g.abs().max().item())
+  out = {}
+  w = H * Dh
+  for j, part in enumerate(("dq", "dk", "dv")):
+    sl = slice(j * w, (j + 1) * w)
+    out[part] = check(dqkv[:, sl], b.g[:, sl], b.g_bound[:, sl], leg, f"{tag} {part}")
+  if delta is not None and b.path != "attn5":
+    out["delta"] = check(delta, b.delta, b.delta_bound, NO_LEGACY, f"{tag} delta")
+  if dbias is not None:
+    ref = dbias_base + b.db
+    bnd = f32_bound(ref, b.db_bound + 2 * U * (abs(dbias_base) + b.db.abs()), F32_ULPS)   # + the add onto the base
+    leg_db = (legacy_db, legacy_db * b.g.abs().sum(0).max().item())
+    for j, part in enumerate(("dbias q", "dbias k", "dbias v")):
+      sl = slice(j * w, (j + 1) * w)
+      out[part] = check(dbias[sl], ref[sl], bnd[sl], leg_db, f"{tag} {part}")
+  return out
+
+
+def check_map_attn_fwd(o, p, q, kv, n, L, H, Dh, lens=None, legacy_p=(1e-3, 1e-5), legacy_o=(1e-2, 1e-2),
+                       name="map attn"):
+  tag = f"{name} [{'map' if Dh == 64 and L <= 2048 else 'map-dh'}]"
+  p_ref, pb, o_ref, ob = map_attn_fwd_bounds(q, kv, n, L, H, Dh, lens)
+  check(p, p_ref, pb, legacy_p, f"{tag} p")
+  check(o, o_ref, ob, legacy_o, f"{tag} o")
+
+
+def check_map_attn_bwd(dq, dkv, q, kv, d_o, n, L, H, Dh, lens=None, legacy=2e-2, name="map attn"):
+  """legacy: the flat tolerance r of the earlier assertions, (r, r max|ref|) per output tensor."""
+  tag = f"{name} [{'map' if Dh == 64 and L <= 2048 else 'map-dh'}]"
+  dq_ref, dqb, dkv_ref, dkvb = map_attn_bwd_bounds(q, kv, d_o, n, L, H, Dh, lens)
+  check(dq, dq_ref, dqb, (legacy, legacy * dq_ref.abs().max().item()), f"{tag} dq")
+  leg = (legacy, legacy * dkv_ref.abs().max().item())
+  w = H * Dh
+  check(dkv[:, :w], dkv_ref[:, :w], dkvb[:, :w], leg, f"{tag} dk")
+  check(dkv[:, w:], dkv_ref[:, w:], dkvb[:, w:], leg, f"{tag} dv")
 
 
 def check_ln_edge_launch(ops, x, scale, bias, dys, dres=None, strided=None, idx=LN_EDGE_IDX, name="ln edge rows"):

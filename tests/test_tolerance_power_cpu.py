@@ -8,9 +8,12 @@ Catalogue notes:
     (bv_common.h mlp_act_from_h, gemm256.hip: gelu' is rounded to bf16 as GELU_GD stores it, so every context kind
     feeds the backward the same bits - test_gemm256_gpu.py asserts MUL(GELU_GD's d) == GELU_BWD bit for bit).  The
     catalogue holds the opposite slip, an unrounded fp32 gelu', which the stage bound rejects.
-  * The attention backward (dqkv) and the column-sum / dW / loss outputs keep their previous tolerances: the model
-    does not justify a tighter bound for them (dqkv goes through bf16 P and dS operands, two contractions and the
-    delta subtraction).  Their mutants below are rejected by those tolerances.
+  * The column-sum / dW / loss outputs keep their previous tolerances: the model does not justify a tighter bound for
+    them.  Their mutants below are rejected by those tolerances.
+  * The attention backward (dq / dk / dv, delta, the bias gradients; MAP p / o / dq / dkv) is held to the models of
+    _bounds.py's attention-backward section.  Every slip is recorded twice: the elements the model rejects and the
+    elements the earlier flat tolerance (3e-2 max|g|) alone would have rejected.  Truncation instead of
+    round-to-nearest-even of the bf16 operands / outputs is recorded as not separable by an elementwise bound.
   * The attention P term is 2^-8 sum P|v|: one round-to-nearest-even of each bf16 P (8 significant bits, unit
     roundoff 2^-8).  A 2^-9 term would reject the prescribed arithmetic itself (err / bound 1.04 on the inputs of
     test_kernels_gpu.py::test_attention[2-64-3]).
@@ -317,31 +320,126 @@ def _attn32(qkv, n, L, H, Dh, lens, scale_after_round=False):
   return rne(o.reshape(n * L, H * Dh)), (m + torch.log(l))[..., 0]
 
 
-def _attn_bwd32(qkv, d_o, n, L, H, Dh, drop_dq_tail=False, drop_dkv_tail=False):
-  """fp32 backward with bf16 P / dS operands (exact fp32 delta), dqkv rounded to bf16."""
+LOG2E = 1.4426950408889634
+
+
+def _attn_bwd32(qkv, d_o, n, L, H, Dh, lens=None, path="attn3 dq+dkv", rb=rne, rb_out=rne, delta_from_o=False,
+                dp_bf16=False, dk_scale=None, dq_scale=None, drop_dq_key=None, drop_dkv_query=None, bwd_lens=None,
+                drop_dq_tail=False, drop_dkv_tail=False):
+  """The backward as the kernels document it, in fp32: lse from the fp32 forward, P = exp2(S c - lse log2 e), delta =
+  fp32 rowsum(P o dP) (path "attn3 dq1...": delta~ = rowsum(dO o bf16 O), eps = rowsum(dS~), the eps correction),
+  dS = P o (dP - delta) ("attn5": from the bf16 P), bf16 P / dS operands, fp32 accumulation, the scale on the
+  accumulator, one rounding to bf16.  Returns (dqkv, delta, bias gradients = column sums of the fp32 accumulators).
+  rb / rb_out: the operand / output rounding (rne, or trunc for the truncation slips); the other keywords are the
+  slips of the catalogue; bwd_lens: key-padding lengths the BACKWARD masks with (the lse stays the forward's)."""
   q, k, v = qkv.float().view(n, L, 3, H, Dh).unbind(2)
   do = d_o.float().view(n, L, H, Dh)
-  sc = 1.0 / math.sqrt(Dh)
-  s = torch.einsum("nqhd,nkhd->nhqk", q, k) * sc
-  p = torch.softmax(s, -1)
+  sc = torch.tensor(1.0 / math.sqrt(Dh), dtype=F32)
+  ar = torch.arange(L)
+  lens = [L] * n if lens is None else lens
+
+  def keymask(ls):
+    return (ar[None, :] < torch.as_tensor(ls)[:, None])[:, None, None, :]
+  st = torch.einsum("nqhd,nkhd->nhqk", q, k)
+  sf = (st * sc).masked_fill(~keymask(lens), float("-inf"))
+  mx = sf.amax(-1, keepdim=True)
+  pf = torch.exp(sf - mx)
+  lsum = pf.sum(-1, keepdim=True)
+  lse = mx + torch.log(lsum)
+  p = torch.exp2(st * (sc * LOG2E) - lse * LOG2E)
+  p = p * keymask(lens if bwd_lens is None else bwd_lens)
   dp = torch.einsum("nqhd,nkhd->nhqk", do, v)
-  delta = (p * dp).sum(-1, keepdim=True)
-  ds = p * (dp - delta)
-  dsq = ds.clone()
-  if drop_dq_tail:
-    dsq[..., L - 1] = 0
-  dq = torch.einsum("nhqk,nkhd->nqhd", rne(dsq), k) * sc
-  dk = torch.einsum("nhqk,nqhd->nkhd", rne(ds), q) * sc
-  dv = torch.einsum("nhqk,nqhd->nkhd", rne(p), do)
+  if dp_bf16:
+    dp = rne(dp)
+  corr = None
+  if delta_from_o or "dq1" in path:
+    o = rne(torch.einsum("nhqk,nkhd->nqhd", rne(pf), v) / lsum.permute(0, 2, 1, 3))
+    dt = (do * o).sum(-1).permute(0, 2, 1)[..., None]
+    if delta_from_o:
+      delta = dt
+    else:
+      eps = (p * (dp - dt)).sum(-1, keepdim=True)
+      delta = dt + eps
+      corr = (dt, eps)
+  else:
+    delta = (p * dp).sum(-1, keepdim=True)
+  pb = rb(p)
+  ds = (pb if path == "attn5" else p) * (dp - delta)
+  if corr is None:
+    dsq = rb(ds)
+    if drop_dq_key is not None:
+      dsq[..., drop_dq_key] = 0
+    if drop_dq_tail:
+      dsq[..., L - 1] = 0
+    dq = torch.einsum("nhqk,nkhd->nqhd", dsq, k)
+  else:
+    dq = torch.einsum("nhqk,nkhd->nqhd", rb(p * (dp - corr[0])), k) - \
+        corr[1].permute(0, 2, 1, 3) * torch.einsum("nhqk,nkhd->nqhd", pb, k)
+  dsk, pv = rb(ds), pb.clone()
+  if drop_dkv_query is not None:
+    dsk[:, :, drop_dkv_query] = 0; pv[:, :, drop_dkv_query] = 0
+  dk = torch.einsum("nhqk,nqhd->nkhd", dsk, q)
+  dv = torch.einsum("nhqk,nqhd->nkhd", pv, do)
+  dq, dk = dq * sc, dk * sc
+  if dq_scale is not None:
+    dq[:, :, dq_scale[0]] *= dq_scale[1]
+  if dk_scale is not None:
+    dk[:, :, dk_scale[0]] *= dk_scale[1]
   if drop_dkv_tail:
     dk[:, L - 1] = 0; dv[:, L - 1] = 0
-  return rne(torch.stack([dq, dk, dv], 2).reshape(n * L, 3 * H * Dh))
+  acc = torch.stack([dq, dk, dv], 2).reshape(n * L, 3 * H * Dh)
+  return rb_out(acc), delta[..., 0], acc.sum(0)
+
+
+def _bwd_inputs(n, L, H, Dh, seed=1, head_scale=False):
+  qkv = B.rnd((n * L, 3 * H * Dh), CPU, seed, 1.5, dtype=BF16)
+  d_o = B.rnd((n * L, H * Dh), CPU, seed + 1, dtype=BF16)
+  return qkv, d_o
+
+
+def _autograd_g(qkv, d_o, n, L, H, Dh, lens=None):
+  qr = qkv.double().requires_grad_(True)
+  q, k, v = qr.view(n, L, 3, H, Dh).unbind(2)
+  s = torch.einsum("nqhd,nkhd->nhqk", q / math.sqrt(Dh), k)
+  if lens is not None:
+    s = s.masked_fill(~(torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None])[:, None, None, :], float("-inf"))
+  torch.einsum("nhqk,nkhd->nqhd", torch.softmax(s, -1), v).reshape(n * L, H * Dh).backward(d_o.double())
+  return qr.grad
+
+
+def _bwd_accept(fam, b, out, legacy=3e-2, legacy_db=2e-2, cap_share=0.01):
+  """The five outputs of an emulation against the model; the legacy cap may apply on at most cap_share of each."""
+  dqkv, delta, db = out
+  leg = (legacy, legacy * b.g.abs().max().item())
+  w = dqkv.shape[1] // 3
+  for j, part in enumerate(("dq", "dk", "dv")):
+    sl = slice(j * w, (j + 1) * w)
+    accept(fam, f"{part} [{b.path}]", dqkv[:, sl], b.g[:, sl], b.g_bound[:, sl], leg)
+    share = B.capped_share(b.g[:, sl], b.g_bound[:, sl], leg)
+    assert share <= cap_share, f"{fam} {part}: the legacy cap applies on {100 * share:.2f}% of the elements"
+  accept(fam, f"delta [{b.path}]", delta, b.delta, b.delta_bound, B.NO_LEGACY)
+  leg_db = (legacy_db, legacy_db * b.g.abs().sum(0).max().item())
+  bnd = B.f32_bound(b.db, b.db_bound)
+  accept(fam, f"bias gradients [{b.path}]", db, b.db, bnd, leg_db)
+  assert B.capped_share(b.db, bnd, leg_db) <= cap_share
+  return leg, leg_db, bnd
+
+
+def _legacy_count(out, ref, legacy):
+  return B.count_rejected(out, ref, torch.full_like(ref, float("inf")), legacy)
+
+
+def _bwd_reject(fam, name, out, ref, bound, legacy):
+  """The model (capped at the legacy tolerance) must reject; the legacy tolerance's own count is recorded next to it."""
+  reject(fam, name, out, ref, bound, legacy)
+  _rec(fam, "  (legacy tolerance alone) " + name, _legacy_count(out, ref, legacy), out.numel())
 
 
 @pytest.mark.parametrize("L", [197, 576])
 def test_attention_bounds_bite(L):
   """Inputs of test_kernels_gpu.py's attention cases (qkv scaled 1.5, seed 1 / 5): o and lse against the contraction
-  model, dqkv against its (unchanged) tolerance; masked with the key-padding lengths of the masked test."""
+  model, dqkv against the backward model (attn_bwd_bounds, capped at the earlier 3e-2 max|g|); masked with the
+  key-padding lengths of the masked test."""
   n, H, Dh = 2, 1, 64
   qkv = B.rnd((n * L, 3 * H * Dh), CPU, 5, 1.5, dtype=BF16)
   lens = [L, L // 3]
@@ -356,19 +454,136 @@ def test_attention_bounds_bite(L):
   os_, ls_ = _attn32(qkv, n, L, H, Dh, lens, scale_after_round=True)
   reject(fam, "o: score scale applied after rounding S to bf16", os_, o_ref, ob, (2e-2, 2e-2))
   reject(fam, "lse: score scale applied after rounding S to bf16", ls_, lse_ref, lb, (1e-4, 1e-3))
-  # backward, unmasked (legacy tolerance 3e-2, 3e-2 max|g|)
-  qkv1 = B.rnd((n * L, 3 * H * Dh), CPU, 1, 1.5, dtype=BF16)
-  d_o = B.rnd((n * L, H * Dh), CPU, 2, dtype=BF16)
-  qr = qkv1.double().requires_grad_(True)
-  q, k, v = qr.view(n, L, 3, H, Dh).unbind(2)
-  s = torch.einsum("nqhd,nkhd->nhqk", q / 8.0, k)
-  torch.einsum("nhqk,nkhd->nqhd", torch.softmax(s, -1), v).reshape(n * L, H * Dh).backward(d_o.double())
-  g = qr.grad
-  leg = (3e-2, 3e-2 * g.abs().max().item())
-  inf = torch.full_like(g, float("inf"))
-  accept(fam, "dqkv: bf16 P / dS operands, fp32 delta", _attn_bwd32(qkv1, d_o, n, L, H, Dh), g, inf, leg)
-  reject(fam, "dQ misses the last key", _attn_bwd32(qkv1, d_o, n, L, H, Dh, drop_dq_tail=True), g, inf, leg)
-  reject(fam, "dK / dV of the last key dropped", _attn_bwd32(qkv1, d_o, n, L, H, Dh, drop_dkv_tail=True), g, inf, leg)
+  # backward, unmasked, at this test's own shape (the catalogue proper is test_attention_backward_bounds_bite)
+  qkv1, d_o = _bwd_inputs(n, L, H, Dh)
+  b = B.attn_bwd_bounds(qkv1, d_o, n, L, H, Dh)
+  g = _autograd_g(qkv1, d_o, n, L, H, Dh)
+  assert (b.g - g).abs().max().item() <= 1e-12 * g.abs().max().item(), "the model's reference is not the gradient"
+  leg, _, _ = _bwd_accept(fam, b, _attn_bwd32(qkv1, d_o, n, L, H, Dh, path=b.path))
+  _bwd_reject(fam, "dQ misses the last key", _attn_bwd32(qkv1, d_o, n, L, H, Dh, path="attn3 dq+dkv",
+                                                         drop_dq_tail=True)[0], b.g, b.g_bound, leg)
+  _bwd_reject(fam, "dK / dV of the last key dropped", _attn_bwd32(qkv1, d_o, n, L, H, Dh, path=b.path,
+                                                                  drop_dkv_tail=True)[0], b.g, b.g_bound, leg)
+
+
+@pytest.mark.parametrize("L,Dh", [(64, 64), (197, 64), (441, 64), (100, 72)])
+def test_attention_backward_bounds_bite(L, Dh):
+  """The backward model (attn_bwd_bounds) on the GPU tests' seeded inputs (qkv seed 1 scaled 1.5, dO seed 2), H = 2.
+  Accepts the documented arithmetic, for dq / dk / dv, delta and the bias gradients, of
+    * the two-sweep path "attn3 dq+dkv" (every masked launch, and unmasked under BV_OPT_ATTN_CFG bits 16 | 128) /
+      "adh" at Dh = 72 - the base model, one rounding of dS;
+    * the path the unmasked shape dispatches to by default (attn5 at L = 64 / 197, the one-sweep dq1 at L = 441);
+    * the masked launches with the key-padding lengths [L, L // 4, L - 1].
+  Rejects the catalogue of slips under the base model, each with the count of the legacy tolerance (3e-2 max|g|)
+  next to it.  Under the attn5 / dq1 variants the same slips are run again: attn5 documents a second 2^-8 rounding
+  of dS (from the bf16 P), which is of the size of the two subtle slips (delta from the bf16 O, dP rounded to bf16),
+  so those two are recorded there without an assertion; every other slip must be rejected there too."""
+  n, H = 2, 2
+  qkv, d_o = _bwd_inputs(n, L, H, Dh)
+  g = _autograd_g(qkv, d_o, n, L, H, Dh)
+  w = H * Dh
+  base = "adh" if Dh != 64 else "attn3 dq+dkv"
+  for path in dict.fromkeys((base, B.attn_bwd_path(L, Dh, False))):
+    fam = f"attn-bwd L{L} Dh{Dh} {path}"
+    b = B.attn_bwd_bounds(qkv, d_o, n, L, H, Dh, path=path)
+    assert (b.g - g).abs().max().item() <= 1e-12 * g.abs().max().item(), "the model's reference is not the gradient"
+    leg, leg_db, db_bnd = _bwd_accept(fam, b, _attn_bwd32(qkv, d_o, n, L, H, Dh, path=path))
+
+    def slip(name, subtle=False, **kw):
+      out = _attn_bwd32(qkv, d_o, n, L, H, Dh, path=path, **kw)[0]
+      if subtle and path != base:
+        _rec(fam, "(recorded) " + name, B.count_rejected(out, b.g, b.g_bound, leg), out.numel())
+        _rec(fam, "  (legacy tolerance alone) " + name, _legacy_count(out, b.g, leg), out.numel())
+      else:
+        _bwd_reject(fam, name, out, b.g, b.g_bound, leg)
+    if "dq1" not in path:   # (dq1 builds delta from the bf16 O by design and corrects it: not a slip there)
+      slip("delta = rowsum(dO o bf16 O)", subtle=True, delta_from_o=True)
+      reject(fam, "the delta buffer itself = rowsum(dO o bf16 O)",
+             _attn_bwd32(qkv, d_o, n, L, H, Dh, path=path, delta_from_o=True)[1], b.delta, b.delta_bound, B.NO_LEGACY)
+    slip("dP rounded to bf16 before the subtraction", subtle=True, dp_bf16=True)
+    slip("dK of head 1 scaled by 0.12 instead of 0.125 (4 %)", dk_scale=(1, 0.96))
+    slip("dQ of head 1 scaled by 0.12 instead of 0.125 (4 %)", dq_scale=(1, 0.96))
+    if "dq1" not in path:   # (the emulation of the eps correction has no per-key dS to drop)
+      slip("dQ misses a middle key", drop_dq_key=L // 2)
+    slip("dK / dV miss one query", drop_dkv_query=L // 2)
+    db = _attn_bwd32(qkv, d_o, n, L, H, Dh, path=path)[2]
+    dbk = db.clone(); dbk[w:2 * w] = db[:w]
+    _bwd_reject(fam, "k-bias gradient of the size of the q-bias gradient", dbk, b.db, db_bnd, leg_db)
+  fam = f"attn-bwd L{L} Dh{Dh}"
+  # masked: the lengths the GPU tests use; two samples at a time (the model and the emulation are per sample)
+  for lens in ([L, L // 4], [L - 1, L // 4]):
+    mfam = f"{fam} lens{lens}"
+    bm = B.attn_bwd_bounds(qkv, d_o, n, L, H, Dh, lens)
+    lm, _, _ = _bwd_accept(mfam, bm, _attn_bwd32(qkv, d_o, n, L, H, Dh, lens, path=bm.path))
+    for d in (1, -1):
+      out = _attn_bwd32(qkv, d_o, n, L, H, Dh, lens, path=bm.path, bwd_lens=[min(L, ln + d) for ln in lens])[0]
+      _bwd_reject(mfam, f"backward key mask off by {d:+d}", out, bm.g, bm.g_bound, lm)
+      if d == 1:
+        pad = out.view(n, L, 3, H, Dh)[1, lens[1]:, 1:]
+        assert (pad != 0).any(), "the off-by-one mask must leave a non-zero dK / dV on a padded key"
+  # truncation instead of round-to-nearest-even, three seeds: an elementwise bound of ~1 bf16 ulp cannot separate a
+  # rounding-mode slip robustly (a truncated operand is off by < 1 ulp, inside 2^-8 sum |dS| |K|); recorded, not asserted
+  for seed in (1, 3, 5):
+    qs, gs = _bwd_inputs(n, L, H, Dh, seed)
+    bs = b if seed == 1 else B.attn_bwd_bounds(qs, gs, n, L, H, Dh)
+    ls = (3e-2, 3e-2 * bs.g.abs().max().item())
+    for what, kw in (("bf16 P / dS operands", dict(rb=trunc)), ("dqkv output", dict(rb_out=trunc))):
+      out = _attn_bwd32(qs, gs, n, L, H, Dh, path=bs.path, **kw)[0]
+      _rec(fam, f"(not separable by an elementwise bound) truncated {what}, seed {seed}",
+           B.count_rejected(out, bs.g, bs.g_bound, ls), out.numel())
+
+
+def _map32(q, kv, d_o, n, L, H, Dh, lens=None, norm_lens=None, centre=True):
+  """attention.hip's MAP kernels in fp32: p = exp(s - max) / sum over the valid keys, o = bf16(sum p v); backward from
+  that p: ds = p (dp - sum p dp), dq, dk, dv rounded once.  norm_lens: lengths the softmax normalises over (slip);
+  centre = False drops the dp - dsum centring of dkv (slip)."""
+  qf = q.float().view(n, H, Dh)
+  k, v = kv.float().view(n, L, 2, H, Dh).unbind(2)
+  do = d_o.float().view(n, H, Dh)
+  sc = torch.tensor(1.0 / math.sqrt(Dh), dtype=F32)
+  lens = [L] * n if lens is None else lens
+  s = torch.einsum("nhd,nkhd->nhk", qf, k) * sc
+  valid = (torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None])[:, None, :]
+  nv = valid if norm_lens is None else (torch.arange(L)[None, :] < torch.as_tensor(norm_lens)[:, None])[:, None, :]
+  e = torch.exp(s.masked_fill(~nv, float("-inf")) - s.masked_fill(~nv, float("-inf")).amax(-1, keepdim=True))
+  p = e * (1.0 / e.sum(-1, keepdim=True)) * valid
+  o = rne(torch.einsum("nhk,nkhd->nhd", p, v)).reshape(n, H * Dh)
+  dp = torch.einsum("nhd,nkhd->nhk", do, v)
+  dsum = (p * dp).sum(-1, keepdim=True)
+  ds = p * (dp - dsum)
+  dq = rne(torch.einsum("nhk,nkhd->nhd", ds, k) * sc).reshape(n, H * Dh)
+  dsk = ds if centre else p * dp
+  dk = dsk.permute(0, 2, 1)[..., None] * (qf * sc)[:, None]
+  dv = p.permute(0, 2, 1)[..., None] * do[:, None]
+  return p, o, dq, rne(torch.stack([dk, dv], 2).reshape(n * L, 2 * H * Dh))
+
+
+@pytest.mark.parametrize("Dh", [64, 72])
+def test_map_attention_bounds_bite(Dh):
+  """MAP attention (test_kernels_gpu.py's inputs: q seed 1, kv seed 2, dO seed 3) at n = 3, L = 70, H = 3, unmasked
+  and with key-padding lengths: p, o, dq, dkv of the fp32 arithmetic are accepted; dkv without the dP - delta
+  centring and p normalised over L instead of kv_len are rejected."""
+  n, L, H = 3, 70, 3
+  q = B.rnd((n, H * Dh), CPU, 1, dtype=BF16)
+  kv = B.rnd((n * L, 2 * H * Dh), CPU, 2, dtype=BF16)
+  d_o = B.rnd((n, H * Dh), CPU, 3, dtype=BF16)
+  for lens in (None, [L, L // 2, L - 1]):
+    fam = f"map Dh{Dh}" + (" masked" if lens else "")
+    p_ref, pb, o_ref, ob = B.map_attn_fwd_bounds(q, kv, n, L, H, Dh, lens)
+    dq_ref, dqb, dkv_ref, dkvb = B.map_attn_bwd_bounds(q, kv, d_o, n, L, H, Dh, lens)
+    lq = (2e-2, 2e-2 * dq_ref.abs().max().item()); lkv = (2e-2, 2e-2 * dkv_ref.abs().max().item())
+    p, o, dq, dkv = _map32(q, kv, d_o, n, L, H, Dh, lens)
+    accept(fam, "p: fp32 softmax", p, p_ref, pb, (1e-3, 1e-5))
+    accept(fam, "o: fp32 p v, one rounding", o, o_ref, ob, (1e-2, 1e-2))
+    accept(fam, "dq", dq, dq_ref, dqb, lq)
+    accept(fam, "dkv", dkv, dkv_ref, dkvb, lkv)
+    for ref, bnd, leg in ((p_ref, pb, (1e-3, 1e-5)), (o_ref, ob, (1e-2, 1e-2)), (dq_ref, dqb, lq), (dkv_ref, dkvb, lkv)):
+      assert B.capped_share(ref, bnd, leg) <= 0.01
+    _bwd_reject(fam, "dkv without the dP - delta centring", _map32(q, kv, d_o, n, L, H, Dh, lens, centre=False)[3],
+                dkv_ref, dkvb, lkv)
+    if lens:
+      _bwd_reject(fam, "p normalised over L instead of kv_len", _map32(q, kv, d_o, n, L, H, Dh, lens,
+                                                                       norm_lens=[L] * n)[0], p_ref, pb, (1e-3, 1e-5))
 
 
 # ---------------------------------------------------------------- losses ----

@@ -202,10 +202,12 @@ int bv_layernorm_bwd_bf16x(const void* dy, int dy_is_f32, const void* x_bf16, co
  * S = (q/sqrt(Dh)) k^T, P = softmax(S), O = P v per (sample, head); no mask, no
  * dropout.  qkv is the packed projection output [n*L][3][H][64] bf16 (row
  * stride 3*H*64); o is [n*L][H][64] bf16; lse is [n][H][L] fp32 (row
- * log-sum-exp, saved for the backward).  Dh must be 64; L <= 576. */
+ * log-sum-exp, saved for the backward).  Dh must be 64; L <= 576.  Extents: exactly n*L rows of qkv are read and of o
+ * written, n*H*L floats of lse; nothing beyond them, whatever the tile sizes of the kernel that runs. */
 int bv_attn_fwd(const void* qkv, void* o, float* lse, int n, int L, int H, void* stream, const bv_ctx* ctx);
 /* dqkv (same layout as qkv) from do ([n*L][H][64] bf16); delta is fp32 scratch
- * [n][H][L] (rowsum(dO*O), computed here).  dbias_rows (optional, fp32 [n][3][H][64]) receives
+ * [n][H][L] (rowsum(dO*O), computed here: n*H*L floats, all written except on the one-launch path below, which keeps
+ * it in LDS and leaves the buffer untouched).  dbias_rows (optional, fp32 [n][3][H][64]) receives
  * the per-sample column sums of dqkv, reduced inside the kernels from the fp32 results; summed
  * over n (bv_colsum) they are the gradient of the query/key/value projection biases
  * (vit.py:93-98) - no separate pass over dqkv.  Precision of dbias_rows on the one-launch path (unmasked
@@ -232,7 +234,7 @@ int bv_attn_bwd_masked(const void* qkv, const void* d_o, const float* lse, const
 
 /* Single-query attention of the MAP head (models/vit.py:176-178): q [n][H][64]
  * bf16, kv packed [n*L][2][H][64] bf16 -> o [n][H][64] bf16, probabilities p
- * [n][H][L] fp32 (saved for the backward). */
+ * [n][H][L] fp32 (saved for the backward; all n*H*L are written, 0 for masked keys). */
 int bv_map_attn_fwd(const void* q, const void* kv, void* o, float* p, int n, int L, int H,
                     void* stream);
 int bv_map_attn_bwd(const void* q, const void* kv, const float* p, const void* d_o, void* dq,
@@ -316,7 +318,7 @@ int bv_concat_cls(const float* cls, const float* x, float* y, int n, int L, int 
 int bv_pool_gap_fwd(const float* x, float* y, int n, int L, int D, void* stream);
 int bv_pool_gap_bwd(const float* dy, float* dx, int n, int L, int D, void* stream);
 /* pooled[i][c] = max_l x[i][l][c] (pool_type "max" / "gmp" of the text tower,
- * models/proj/image_text/text_transformer.py:89-90); argmax [n][D] int32 keeps the position of the (first) maximum,
+ * models/proj/image_text/text_transformer.py:89-90); argmax [n][D] int32 (n*D elements, all written) keeps the position of the (first) maximum,
  * the backward writes dy[i][c] there and 0 to the other L - 1 positions; fp32. */
 int bv_pool_max_fwd(const float* x, float* y, int* argmax, int n, int L, int D, void* stream);
 int bv_pool_max_bwd(const float* dy, const int* argmax, float* dx, int n, int L, int D, void* stream);
@@ -337,7 +339,7 @@ int bv_l2norm_bwd(const float* z, const float* norm, const float* dzn, float* dz
  * zimg_local . ztxt_all^T [n][B] fp32 on entry; on exit it holds
  * G = dL/dS = -(1/B_global) * m * sigmoid(-m*S), S = t*raw + b, m = +1 on the
  * positive diagonal (column row_offset + i) else -1.
- * stats is double[3] (device), ACCUMULATED:
+ * stats is double[3] (device: 3 doubles, nothing beyond), ACCUMULATED:
  * stats[0] += sum_ij -log_sigmoid(m*S) / B_global   (this rank's loss share)
  * stats[1] += sum_ij G*(S-b)   (= dL/dt', t = exp(t'))
  * stats[2] += sum_ij G         (= dL/db)
@@ -349,8 +351,8 @@ int bv_siglip_loss(float* raw, const float* t_param, const float* b_param, doubl
  * (trainers/proj/image_text/_deprecated_contrastive.py:143-160): for logits = exp(t') raw + b of this
  * rank's n images against all B texts (raw as passed to bv_siglip_loss, BEFORE it is overwritten),
  * out9 = {pos_min, pos_max, pos_avg, local_neg_min, local_neg_max, local_neg_avg, neg_min, neg_max,
- * neg_avg}; "local" = the n x n block of this rank's own texts (columns row_offset ..).  part is
- * scratch of BV_LOGIT_STATS_BLOCKS * 9 floats. */
+ * neg_avg}; "local" = the n x n block of this rank's own texts (columns row_offset ..).  out9 is 9 floats, all
+ * written; part is scratch of exactly BV_LOGIT_STATS_BLOCKS * 9 floats (need not be initialised). */
 #define BV_LOGIT_STATS_BLOCKS 512
 int bv_logit_stats(const float* raw, const float* t_param, const float* b_param, float* part, float* out9,
                    int n, int B, int row_offset, void* stream);
@@ -385,7 +387,8 @@ int bv_tanh_bwd(const float* y, const float* dy, float* dx, long count, void* st
  *                    addend = the stream; backward: x = the stream's gradient, out_bf16 = the branch's GEMM operand.
  *   bv_dropout_bf16: a (and b, may be NULL) *= keep / (1 - rate) in place, bf16, the SAME bits on both (gelu(h) and the
  *                    stored gelu'(h): the backward's product then carries the mask).
- *   bv_dropout_mask: keep_u8[i] = the bit of element i (parity tests hand the masks to the oracle).
+ *   bv_dropout_mask: keep_u8[i] = the bit of element i, one byte (0 / 1) per element, `count` bytes (parity tests hand
+ *                    the masks to the oracle).
  * count: elements, a multiple of 4. */
 int bv_dropout_f32(const float* x, const float* addend, float* out_f32, void* out_bf16, long count,
                    unsigned long long key, float rate, void* stream);
@@ -475,7 +478,7 @@ int bv_adafactor_step(float* params, const float* grads, void* momentum, int mom
                       const float* sched /*host*/, int nsched, double* stats,
                       float block_rms_clip /* scale_by_adafactor(clipping_threshold=...) = optax.clip_by_block_rms per leaf
                                               (optax.py:190,208); <= 0: off */,
-                      double* block_usq /* device scratch [nleaves] when block_rms_clip > 0, else NULL */, void* stream);
+                      double* block_usq /* device scratch, nleaves doubles, when block_rms_clip > 0, else NULL */, void* stream);
 
 /* ------------------------------------------------------- Collectives (RCCL) ----
  * The exchange steps of the data-parallel step for hosts that do not go through torch.distributed (the

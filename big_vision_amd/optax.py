@@ -93,6 +93,78 @@ def factored_dims(shape, min_dim_size_to_factor=32):
   return int(order[-2]), int(order[-1])
 
 
+def af_view(leaf, shape, strides, fd):
+  """A leaf of `shape` / `strides` (elements) as the strided [B1][B2][R][C] view of bv_adafactor_leaf, fd =
+  factored_dims(shape): (B1, B2, R, C, sB1, sB2, sR, sC, rest) with rest the non-trivial axes outside the factored
+  pair.  Factored: C = the largest axis (d0), R = the second largest (d1), B1 / B2 the remaining ones; unfactored: the
+  (up to four) non-trivial axes in order, the last one as C."""
+  if fd is None:
+    rest = list(range(len(shape)))
+    R = C = 1
+    sR = sC = 0
+  else:
+    d1, d0 = fd
+    rest = [a for a in range(len(shape)) if a not in fd]
+    R, C, sR, sC = shape[d1], shape[d0], strides[d1], strides[d0]
+  rest = [a for a in rest if shape[a] > 1]
+  if fd is None:
+    # unfactored: enumerate the elements through (up to) four axes, last one as "C"
+    axes = rest[-4:] if len(rest) <= 4 else None
+    if axes is None:
+      raise NotImplementedError(f"{leaf}: more than 4 non-trivial axes")
+    ext = [1] * (4 - len(axes)) + [shape[a] for a in axes]
+    strd = [0] * (4 - len(axes)) + [strides[a] for a in axes]
+    B1, B2, R, C = ext
+    sB1, sB2, sR, sC = strd
+  else:
+    if len(rest) > 2:
+      raise NotImplementedError(f"{leaf} {shape}: more than two axes besides the factored pair")
+    ext = [1] * (2 - len(rest)) + [shape[a] for a in rest]
+    strd = [0] * (2 - len(rest)) + [strides[a] for a in rest]
+    (B1, B2), (sB1, sB2) = ext, strd
+  return B1, B2, R, C, sB1, sB2, sR, sC, rest
+
+
+# struct bv_af_leaf (include/bvhip.h)
+AF_LEAF = np.dtype([("off", np.int64), ("sB1", np.int64), ("sB2", np.int64), ("sR", np.int64), ("sC", np.int64),
+                    ("soff", np.int64), ("B1", np.int32), ("B2", np.int32), ("R", np.int32), ("C", np.int32),
+                    ("factored", np.int32), ("sched_idx", np.int32), ("r_fast", np.int32), ("pad_", np.int32),
+                    ("lr_eff", np.float32), ("wd", np.float32)], align=True)
+assert AF_LEAF.itemsize == 88, AF_LEAF.itemsize
+
+
+def af_table(own):
+  """The leaf table of the batched Adafactor step for the leaf records `own` (dicts with view, factored, soff, sched,
+  lr_eff, wd, B, R, C): (table as an AF_LEAF array, size classes, the records in table order).
+  The batched kernel (ops.adafactor_step_) launches a 2-D grid (extent of the LARGEST leaf of the table) x (leaves),
+  and a workgroup beyond its own leaf's extent returns at once: with one table for the whole model the 300 biases /
+  LayerNorm scales would each pay for the embedding table's 32 000 rows (~10 M empty workgroups per step at B/16 +
+  text).  The table is therefore sorted by extent and cut into SIZE CLASSES (a new class where the row count or the
+  element count drops below a quarter of the class's largest; unfactored leaves apart, they skip the three statistics
+  launches); one call of it per class, sized for that class.  The update does not depend on the order."""
+  def extents(lf):
+    B = lf["B"]
+    return (B * lf["R"], B * lf["C"], B, B * lf["R"] * lf["C"])
+  own = sorted(own, key=lambda lf: (not lf["factored"], -extents(lf)[3], -extents(lf)[0]))
+  tab = np.zeros(max(1, len(own)), AF_LEAF)
+  classes = []     # (first row of the table, rows, {rows, cols, b, total} grid extents)
+  for i, lf in enumerate(own):
+    off, B1, B2, R, C, sB1, sB2, sR, sC = (int(x) for x in lf["view"])
+    tab[i] = (off, sB1, sB2, sR, sC, lf["soff"], B1, B2, R, C, int(lf["factored"]), lf["sched"], int(sR < sC), 0,
+              lf["lr_eff"], lf["wd"])
+    rows, cols, b, total = extents(lf)
+    cur = classes[-1] if classes else None
+    if (cur is None or cur["factored"] != lf["factored"] or total * 4 < cur["total"]
+        or (lf["factored"] and rows * 4 < cur["rows"])):
+      cur = dict(first=i, n=0, factored=lf["factored"], rows=0, cols=0, b=0, total=0)
+      classes.append(cur)
+    cur["n"] += 1
+    if lf["factored"]:
+      cur["rows"], cur["cols"], cur["b"] = max(cur["rows"], rows), max(cur["cols"], cols), max(cur["b"], b)
+    cur["total"] = max(cur["total"], total)
+  return tab, classes, own
+
+
 def frozen_patterns(config) -> List[str]:
   """Regexes of config.schedule whose schedule is None (= frozen params).
 
@@ -586,31 +658,7 @@ class Adafactor(Optimizer):
               f"{st.ext_of[leaf]}: stacked (scan) leaf {(len(group),) + shape} factors over axes {fd_st} in optax "
               f"(the depth axis {len(group)} >= min_dim_size_to_factor enters the factored pair); per-block "
               "Adafactor statistics would differ from big_vision's - not implemented")
-      if fd is None:
-        d1 = d0 = None
-        rest = list(range(len(shape)))
-        R = C = 1
-        sR = sC = 0
-      else:
-        d1, d0 = fd
-        rest = [a for a in range(len(shape)) if a not in fd]
-        R, C, sR, sC = shape[d1], shape[d0], strides[d1], strides[d0]
-      rest = [a for a in rest if shape[a] > 1]
-      if fd is None:
-        # unfactored: enumerate the elements through (up to) four axes, last one as "C"
-        axes = rest[-4:] if len(rest) <= 4 else None
-        if axes is None:
-          raise NotImplementedError(f"{leaf}: more than 4 non-trivial axes")
-        ext = [1] * (4 - len(axes)) + [shape[a] for a in axes]
-        strd = [0] * (4 - len(axes)) + [strides[a] for a in axes]
-        B1, B2, R, C = ext
-        sB1, sB2, sR, sC = strd
-      else:
-        if len(rest) > 2:
-          raise NotImplementedError(f"{leaf} {shape}: more than two axes besides the factored pair")
-        ext = [1] * (2 - len(rest)) + [shape[a] for a in rest]
-        strd = [0] * (2 - len(rest)) + [strides[a] for a in rest]
-        (B1, B2), (sB1, sB2) = ext, strd
+      B1, B2, R, C, sB1, sB2, sR, sC, rest = af_view(leaf, shape, strides, fd)
       B = B1 * B2
       n_state = (B * R + B * C + B) if fd is not None else B * R * C
       view = (ctypes.c_long * 9)(e.offset + v.storage_offset(), B1, B2, R, C, sB1, sB2, sR, sC)
@@ -623,11 +671,6 @@ class Adafactor(Optimizer):
     self.af_state = torch.zeros(max(4, off_state), device=dev, dtype=torch.float32)
     # device table of all leaves (struct bv_af_leaf, include/bvhip.h) for the batched step: four launches per
     # step instead of up to four per leaf
-    AF_LEAF = np.dtype([("off", np.int64), ("sB1", np.int64), ("sB2", np.int64), ("sR", np.int64), ("sC", np.int64),
-                        ("soff", np.int64), ("B1", np.int32), ("B2", np.int32), ("R", np.int32), ("C", np.int32),
-                        ("factored", np.int32), ("sched_idx", np.int32), ("r_fast", np.int32), ("pad_", np.int32),
-                        ("lr_eff", np.float32), ("wd", np.float32)], align=True)
-    assert AF_LEAF.itemsize == 88, AF_LEAF.itemsize
     own = [lf for lf in self.af_leaves if lf["own"]]   # the leaves this rank updates (all of them when replicated)
     # the own-run buffers (fp32 master, momentum) reach the kernel as base pointers shifted by -lo (_update):
     # every row of this rank's table must address elements of [lo, hi) only
@@ -635,32 +678,7 @@ class Adafactor(Optimizer):
       e = st.entries[st.leaf_index[lf["leaf"]][0]]
       assert self.lo <= e.offset and e.offset + e.numel <= self.hi, (lf["leaf"], e.offset, e.numel, self.lo, self.hi)
     self.af_nown = len(own)
-    # The batched kernel (ops.adafactor_step_) launches a 2-D grid (extent of the LARGEST leaf of the table) x (leaves), and a workgroup beyond
-    # its own leaf's extent returns at once: with one table for the whole model the 300 biases / LayerNorm scales would
-    # each pay for the embedding table's 32 000 rows (~10 M empty workgroups per step at B/16 + text).  The table is
-    # therefore sorted by extent and cut into SIZE CLASSES (a new class where the row count or the element count
-    # drops below a quarter of the class's largest; unfactored leaves apart, they skip the three statistics launches);
-    # one call of it per class, sized for that class.  The update does not depend on the order.
-    def extents(lf):
-      B = lf["B"]
-      return (B * lf["R"], B * lf["C"], B, B * lf["R"] * lf["C"])
-    own.sort(key=lambda lf: (not lf["factored"], -extents(lf)[3], -extents(lf)[0]))
-    tab = np.zeros(max(1, len(own)), AF_LEAF)
-    self.af_classes = []     # (first row of the table, rows, {rows, cols, b, total} grid extents)
-    for i, lf in enumerate(own):
-      off, B1, B2, R, C, sB1, sB2, sR, sC = (int(x) for x in lf["view"])
-      tab[i] = (off, sB1, sB2, sR, sC, lf["soff"], B1, B2, R, C, int(lf["factored"]), lf["sched"], int(sR < sC), 0,
-                lf["lr_eff"], lf["wd"])
-      rows, cols, b, total = extents(lf)
-      cur = self.af_classes[-1] if self.af_classes else None
-      if (cur is None or cur["factored"] != lf["factored"] or total * 4 < cur["total"]
-          or (lf["factored"] and rows * 4 < cur["rows"])):
-        cur = dict(first=i, n=0, factored=lf["factored"], rows=0, cols=0, b=0, total=0)
-        self.af_classes.append(cur)
-      cur["n"] += 1
-      if lf["factored"]:
-        cur["rows"], cur["cols"], cur["b"] = max(cur["rows"], rows), max(cur["cols"], cols), max(cur["b"], b)
-      cur["total"] = max(cur["total"], total)
+    tab, self.af_classes, _ = af_table(own)
     self.af_table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev).view(-1, AF_LEAF.itemsize)
     # (sharded: the momentum of the OWN run of tensors only - elements [lo, hi) of the flat index space)
     n_mu = max(4, self.hi - self.lo) if self.sharded else st.trainable_count

@@ -26,6 +26,7 @@ what share of the elements the legacy cap (not the model) applies.  NaN / Inf in
 import collections
 import math
 
+import numpy as np
 import torch
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
@@ -95,6 +96,53 @@ def sigmoid_xent_extreme_inputs(dev, n=4, C=300):
   logits[1] = 120.0 * torch.sign(rnd((C,), dev, 87))
   labels = torch.rand((n, C), generator=torch.Generator().manual_seed(88)).to(dev)
   return logits, labels
+
+
+def opt_inputs(n, dev, seed, zero_grad=False):
+  """(p, g) of the optimizer tests, fp32: parameters cycling through p = 0, |p| ~ 1e-4 (the update is resolved to
+  ulps there, not to ulp(p)), |p| ~ 1 and a few |p| ~ 30; gradients of scale 1e-3 with a few exact zeros and a few
+  1e-12 elements."""
+  p = rnd((n,), "cpu", seed)
+  k = torch.arange(n) % 8
+  p = torch.where(k == 0, torch.zeros_like(p), torch.where(k < 3, p * 1e-4, p))
+  p[5::61] = 30.0 * torch.sign(rnd((n,), "cpu", seed + 7))[5::61]
+  g = rnd((n,), "cpu", seed + 1, 1e-3)
+  g[3::37] = 0.0
+  g[11::41] = 1e-12
+  if zero_grad:
+    g.zero_()
+  return p.to(dev), g.to(dev)
+
+
+# Adafactor leaves of the optimizer tests: (name, buffer shape, index into it giving the leaf, gradient edit).  The
+# leaf is the indexed view of a contiguous buffer, so its strides / offset are those of a slice of a fused or padded
+# tensor; factored_dims + af_view (big_vision_amd/optax.py) turn it into the kernel's [B1][B2][R][C] view.
+_S = slice
+AF_SPECS = [
+    ("32x33", (32, 33), (), None), ("33x32", (33, 32), (), None), ("32x257", (32, 257), (), None),
+    ("300x64", (300, 64), (), None), ("64x64", (64, 64), (), None),
+    ("qkv-query", (128, 3, 2, 64), (_S(None), 0), None), ("qkv-key", (128, 3, 2, 64), (_S(None), 1), None),
+    ("2x3x32x40-padded", (2, 5, 34, 48), (_S(None), _S(1, 4), _S(1, 33), _S(3, 43)), None),
+    ("one", (1,), (), None), ("100", (100,), (), None), ("257", (257,), (), None), ("31x500", (31, 500), (), None),
+    ("2x3x5x7", (2, 3, 5, 7), (), None),
+    ("40x48-zero-row-col", (40, 48), (), "rowcol"), ("32x36-zero-grad", (32, 36), (), "zero"),
+]
+
+
+def af_leaf_inputs(spec, dev, seed):
+  """Buffers (flat fp32 p, g of the whole buffer) and the leaf's (shape, strides, offset) for one AF_SPECS entry."""
+  name, bshape, index, edit = spec
+  n = math.prod(bshape)
+  p, g = opt_inputs(n, "cpu", seed)
+  t = torch.empty(bshape, device="meta")[index]
+  shape, strides, off = tuple(t.shape), tuple(t.stride()), t.storage_offset()
+  gv = g.as_strided(shape, strides, off)
+  if edit == "zero":
+    gv.zero_()
+  elif edit == "rowcol":
+    gv[3, :] = 0.0
+    gv[:, 5] = 0.0
+  return p.to(dev), g.to(dev), shape, strides, off
 
 
 # ------------------------------------------------------------------ units ----
@@ -588,6 +636,308 @@ def map_attn_bwd_bounds(q, kv, d_o, n, L, H, Dh, lens=None):
 
 
 
+# -------------------------------------------------------------- optimizer ----
+# loss_optim.hip opt_chain (bv_adam_step, bv_trace_step) and adafactor.hip (bv_adafactor_leaf, bv_adafactor_step), per
+# element, every operation fp32 (the compiler may contract a multiply-add into one fma: one rounding fewer, never more):
+#   clip    gn = (float) sqrt(gsq) (fp64 sqrt, one rounding to fp32); clip = gn > clip_norm ? clip_norm / gn : 1, so
+#           gn == clip_norm is the NO-clip side; g' = g clip                          (loss_optim.hip:416-420, 445)
+#   adam    m' = b1 m + (1 - b1) g'; v' = b2 v + ((1 - b2) g') g'; u = (m' / bc1) / (sqrtf(v' / bc2) + eps): eps
+#           OUTSIDE the root, after the bc2 division; u from the UNROUNDED m'          (loss_optim.hip:451-453)
+#   trace   t' = g' + beta t; u = nesterov ? g' + beta t' (the unrounded t') : t'     (loss_optim.hip:456-457)
+#   tail    d = (lr_eff u + wd_eff p) sched; p' = p - d; m' / t' stored fp32 or as ONE round-to-nearest-even to bf16;
+#           shadow = rne(p'); stats += sum p'^2, sum d^2: fp32 over a thread's 4 elements, then fp64
+#                                                                                     (loss_optim.hip:461-496)
+#   adafactor  x = g clip; v_row' = d v_row + (1 - d) (sum_C (x^2 + eps) / C); v_col' likewise over R; rcm = sum_R
+#           v_row' / R; u = (x rsqrtf(v_row' / rcm)) rsqrtf(v_col'), or u = x rsqrtf(v'), v' = d v + (1 - d)(x^2 + eps);
+#           [u *= 1 / fmaxf(1, sqrtf((float)(usq / total)) / threshold), usq = sum u^2 over the whole LEAF]; m' =
+#           mom m + (1 - mom) u (stored by RNE, used unrounded); upd = -sched (lr_eff m' + wd p); p' = p + upd
+#                                                                                     (adafactor.hip:53-58, 73-86, 111-139, 274-318)
+# Errors are propagated as ABSOLUTE errors (b1 m + (1 - b1) g cancels).  One fp32 rounding of x is charged U |x|.
+# Device sqrtf, `/` and rsqrtf are charged DEV_ULPS = 2 ulps per call: no accuracy table of the device math library is
+# installed with the toolchain, so this is the fallback constant of the issue, not a figure fitted to any kernel
+# output (hipcc's default is a correctly rounded `/` and sqrtf and a 1-ulp rsqrtf).  The fp64 sqrt of the clip is taken
+# as correctly rounded.
+DEV_ULPS = 2
+Out = collections.namedtuple("Out", "ref bound lo_hi")
+_TINY = 2.0 ** -150
+
+
+def _rd(x):
+  """One fp32 rounding of a value of magnitude |x| (half an ulp <= U |x|)."""
+  return U * x.abs() + _TINY
+
+
+def _dv(x):
+  """One device sqrtf / divide / rsqrtf result of magnitude |x|: DEV_ULPS ulps (ulp <= 2 U |x|)."""
+  return DEV_ULPS * 2 * U * x.abs() + _TINY
+
+
+def f32s(x):
+  """A python scalar as the C ABI receives it (float)."""
+  return float(np.float32(x))
+
+
+def clip_factor(gsq, clip_norm):
+  """(clip, e_clip) of the global-norm clip exactly as the kernels branch: clip_norm / float32(sqrt(gsq)) only when
+  float32(sqrt(gsq)) > clip_norm, else exactly 1 with no error."""
+  cn = np.float32(clip_norm or 0.0)
+  if not cn > 0:
+    return 1.0, 0.0
+  gn = np.float32(np.sqrt(np.float64(gsq)))
+  if not gn > cn:
+    return 1.0, 0.0
+  c = float(cn / gn)
+  return c, DEV_ULPS * 2 * U * c
+
+
+def _t(x, like):
+  return torch.as_tensor(x, dtype=F64, device=like.device) if not torch.is_tensor(x) else x.double().to(like.device)
+
+
+def _scaled_grad(g, clip, e_clip):
+  g = g.double()
+  if clip == 1.0 and e_clip == 0.0:
+    return g, torch.zeros_like(g)          # g * 1.f is exact
+  gc = g * clip
+  return gc, g.abs() * e_clip + _rd(gc)
+
+
+def _apply(p, u, e_u, lr, wd, sched):
+  """d = (lr u + wd p) sched, p' = p - d: (p', e_p, d, e_d)."""
+  lr, wd, sched = _t(lr, p), _t(wd, p), _t(sched, p)
+  a = lr * u
+  e_a = lr.abs() * e_u + _rd(a)
+  b = wd * p
+  c = a + b
+  e_c = e_a + _rd(b)
+  e_c = e_c + _rd(c.abs() + e_c)
+  d = sched * c
+  e_d = sched.abs() * e_c
+  e_d = e_d + _rd(d.abs() + e_d)
+  pn = p - d
+  e_p = e_d + _rd(pn.abs() + e_d)
+  return pn, e_p, d, e_d
+
+
+def _sumsq(x, e, K):
+  """sum x^2 of values within e of x, fp32 partial sums of K non-negative terms, then fp64: (ref, bound)."""
+  ref = (x * x).sum()
+  return ref, (2 * x.abs() * e + e * e).sum() + (gamma(K) + 2) * U * ref + 1e-13 * ref + 1e-300
+
+
+def _store(ref, e, bf16):
+  """A stored accumulator: fp32 -> bound e; bf16 -> one RNE of a value within e of ref: bound 0.5 ulp + e and the
+  interval [rne(ref - e), rne(ref + e)] (almost everywhere one bf16 number)."""
+  if not bf16:
+    return Out(ref, e, None)
+  return Out(ref, bf16_bound(ref, e), (rne_bf16(ref - e), rne_bf16(ref + e)))
+
+
+def _sqrt_err(v, e):
+  """|sqrt(v~) - sqrt(v)| for |v~ - v| <= e, v >= 0 (sqrt is not Lipschitz at 0)."""
+  s = v.sqrt()
+  return torch.maximum((v + e).sqrt() - s, s - (v - e).clamp_min(0).sqrt())
+
+
+def adam_bounds(p, g, mu, nu, lr_eff, wd_eff, sched, gsq, clip_norm, b1, b2, eps, bc1, bc2):
+  """OPT_ADAM on the stored inputs (fp32 p, g, nu; mu fp32 or bf16; lr_eff / wd_eff / sched scalars or per-element
+  tensors of the fp32 values the kernel reads; fp64 gsq).  Returns {"mu", "nu", "p": Out, "stats": (ref[2], bound[2])}."""
+  clip, e_clip = clip_factor(gsq, clip_norm)
+  mu_bf16 = mu.dtype == BF16
+  p, m, v = p.double(), mu.double(), nu.double()
+  b1, b2, eps, bc1, bc2 = (f32s(x) for x in (b1, b2, eps, bc1, bc2))
+  ob1 = float(np.float32(1) - np.float32(b1)); ob2 = float(np.float32(1) - np.float32(b2))
+  gc, e_g = _scaled_grad(g, clip, e_clip)
+  t1, t2 = b1 * m, ob1 * gc
+  mn = t1 + t2
+  e_m = _rd(t1) + ob1 * e_g + _rd(t2)
+  e_m = e_m + _rd(mn.abs() + e_m)
+  s1 = ob2 * gc
+  s2 = s1 * gc
+  t3 = b2 * v
+  vn = t3 + s2
+  e_v = _rd(t3) + 2 * ob2 * gc.abs() * e_g + ob2 * e_g * e_g + _rd(s1) * gc.abs() + _rd(s2)
+  e_v = e_v + _rd(vn + e_v)
+  mh = mn / bc1
+  e_mh = e_m / bc1 + _dv(mh)
+  vh = vn / bc2
+  e_vh = e_v / bc2 + _dv(vh)
+  sq = vh.sqrt()
+  e_sq = _sqrt_err(vh, e_vh) + _dv(sq)
+  den = sq + eps
+  e_den = e_sq + _rd(den)
+  den_lo = (den - e_den).clamp_min(_TINY)
+  u = mh / den
+  e_u = e_mh / den_lo + mh.abs() * e_den / (den * den_lo) + _dv(u.abs() + e_mh / den_lo)
+  pn, e_p, d, e_d = _apply(p, u, e_u, lr_eff, wd_eff, sched)
+  sp, bp = _sumsq(pn, e_p, 4)
+  su, bu = _sumsq(d, e_d, 4)
+  return {"mu": _store(mn, e_m, mu_bf16), "nu": Out(vn, e_v, None), "p": Out(pn, e_p, None),
+          "stats": (torch.stack([sp, su]), torch.stack([bp, bu]))}
+
+
+def trace_bounds(p, g, trace, lr_eff, wd_eff, sched, gsq, clip_norm, beta, nesterov):
+  """OPT_TRACE (trace: the stored bf16 / fp32 accumulator) or OPT_IDENTITY (trace None): {"trace" (absent for
+  identity), "p": Out, "stats"}."""
+  clip, e_clip = clip_factor(gsq, clip_norm)
+  p = p.double()
+  gc, e_g = _scaled_grad(g, clip, e_clip)
+  out = {}
+  if trace is None:
+    u, e_u = gc, e_g
+  else:
+    beta = f32s(beta)
+    bt = beta * trace.double()
+    tn = gc + bt
+    e_t = e_g + _rd(bt)
+    e_t = e_t + _rd(tn.abs() + e_t)
+    out["trace"] = _store(tn, e_t, trace.dtype == BF16)
+    if nesterov:
+      bn = beta * tn
+      u = gc + bn
+      e_u = e_g + abs(beta) * e_t + _rd(bn)
+      e_u = e_u + _rd(u.abs() + e_u)
+    else:
+      u, e_u = tn, e_t
+  pn, e_p, d, e_d = _apply(p, u, e_u, lr_eff, wd_eff, sched)
+  sp, bp = _sumsq(pn, e_p, 4)
+  su, bu = _sumsq(d, e_d, 4)
+  out["p"] = Out(pn, e_p, None)
+  out["stats"] = (torch.stack([sp, su]), torch.stack([bp, bu]))
+  return out
+
+
+def sqnorm_bound(x):
+  """bv_sqnorm: float4 loads, 4 squares added per iteration into an fp32 per-thread partial over the grid-stride
+  range ((count / 4) / (256 x 2048 workgroups) iterations), the scalar tail on workgroup 0, an 8-add workgroup tree,
+  fp64 atomics: (ref, bound) - an fp32 sum of non-negative terms of the per-thread length."""
+  n = x.numel()
+  n4 = n // 4
+  grid = min(max((n4 + 255) // 256, 1), 2048)
+  K = 4 * (-(-n4 // (256 * grid))) + 1 + 8          # per-thread terms (+ its tail element) + the tree
+  ref = (x.double() ** 2).sum()
+  return ref, (gamma(K) + 1) * U * ref + 1e-13 * ref + 1e-300
+
+
+def _rsqrt_err(q, e_q):
+  r = q.rsqrt()
+  return (q - e_q).clamp_min(_TINY).rsqrt() - r + _dv(r)
+
+
+def _af_stats_K(total, cap):
+  grid = min(-(-total // 1024), cap)
+  return -(-total // (256 * grid)) + 8
+
+
+def adafactor_bounds(p, g, mom, state, factored, gsq, clip_norm, decay, eps, momentum, lr_eff, wd, sched,
+                     block_rms_clip=0.0, grid_cap=2048):
+  """One Adafactor leaf.  p, g, mom: the leaf's [B1][B2][R][C] views of the buffers as stored before the step (mom
+  bf16 or fp32); state: its fp32 statistics before the step (factored: v_row [B R], v_col [B C], rcm [B]; else v
+  [B R C] in the view's order).  Returns {"v_row", "v_col", "rcm" | "v", "mom", "p": Out, "stats": (ref[2], bound[2]),
+  and with block_rms_clip > 0 "usq": (ref, bound), "scale": (ref, bound)}, the tensors in the view's [B1][B2][R][C]
+  shape ([B, R] / [B, C] / [B] for the factored statistics)."""
+  clip, e_clip = clip_factor(gsq, clip_norm)
+  B1, B2, R, C = p.shape
+  Bn = B1 * B2
+  total = Bn * R * C
+  decay, eps, momentum = f32s(decay), f32s(eps), f32s(momentum)
+  od = float(np.float32(1) - np.float32(decay)); om = float(np.float32(1) - np.float32(momentum))
+  x, e_x = _scaled_grad(g.reshape(Bn, R, C), clip, e_clip)
+  pd = p.double().reshape(Bn, R, C)
+  st = state.double()
+  out = {}
+  sqe = x * x + eps                                  # each term: the square, the + eps
+  e_sqe = 2 * x.abs() * e_x + e_x * e_x + 2 * U * sqe
+
+  def ema(old, s, e_s, K, n):
+    s_e = e_s + gamma(K) * U * s                     # K-term fp32 sum of non-negative terms
+    mean = s / n
+    e_mean = s_e / n + _dv(mean)
+    t1, t2 = decay * old, od * mean
+    new = t1 + t2
+    e = _rd(t1) + od * e_mean + _rd(t2)
+    return new, e + _rd(new + e)
+
+  if factored:
+    v_row, v_col = st[:Bn * R].view(Bn, R), st[Bn * R:Bn * R + Bn * C].view(Bn, C)
+    vr, e_vr = ema(v_row, sqe.sum(2), e_sqe.sum(2), C, C)
+    vc, e_vc = ema(v_col, sqe.sum(1), e_sqe.sum(1), R, R)
+    rs = vr.sum(1)
+    rcm = rs / R
+    e_rcm = (e_vr.sum(1) + gamma(R) * U * rs) / R + _dv(rcm)
+    out["v_row"], out["v_col"], out["rcm"] = Out(vr, e_vr, None), Out(vc, e_vc, None), Out(rcm, e_rcm, None)
+    rcm_lo = (rcm - e_rcm).clamp_min(_TINY)
+    q = vr / rcm[:, None]
+    e_q = e_vr / rcm_lo[:, None] + vr * (e_rcm / (rcm * rcm_lo))[:, None] + _dv(q)
+    rf, e_rf = q.rsqrt(), _rsqrt_err(q, e_q)
+    cf, e_cf = vc.rsqrt(), _rsqrt_err(vc, e_vc)
+    xr = x * rf[:, :, None]
+    e_xr = e_x * rf[:, :, None] + (x.abs() + e_x) * e_rf[:, :, None] + _rd(xr)
+    u = xr * cf[:, None, :]
+    e_u = e_xr * cf[:, None, :] + (xr.abs() + e_xr) * e_cf[:, None, :]
+    e_u = e_u + _rd(u.abs() + e_u)
+  else:
+    v = st[:total].view(Bn, R, C)
+    t1, t2 = decay * v, od * sqe
+    nv = t1 + t2
+    e_nv = _rd(t1) + od * e_sqe + _rd(t2)
+    e_nv = e_nv + _rd(nv + e_nv)
+    out["v"] = Out(nv.view(B1, B2, R, C), e_nv.view(B1, B2, R, C), None)
+    rq, e_rq = nv.rsqrt(), _rsqrt_err(nv, e_nv)
+    u = x * rq
+    e_u = e_x * rq + (x.abs() + e_x) * e_rq
+    e_u = e_u + _rd(u.abs() + e_u)
+  if block_rms_clip and block_rms_clip > 0:
+    thr = f32s(block_rms_clip)
+    usq, e_usq = _sumsq(u, e_u, _af_stats_K(total, 1024))
+    out["usq"] = (usq, e_usq)
+    def scale_of(s, sign):                           # monotone decreasing in s; sign: -1 lower / +1 upper end
+      rms = (s.clamp_min(0) / total).sqrt()
+      ratio = rms / thr * (1 - sign * (2 * DEV_ULPS * 2 + 1) * U)       # float(), sqrtf, the divide
+      return torch.where(ratio > 1, (1 / ratio) * (1 + sign * DEV_ULPS * 2 * U), torch.ones_like(ratio))
+    rms32 = np.float32(np.sqrt(np.float32(usq.item() / total)))
+    ratio32 = rms32 / np.float32(thr)
+    bs = float(np.float32(1) / max(np.float32(1), ratio32))
+    lo, hi = scale_of(usq + e_usq, -1).item(), scale_of(usq - e_usq, +1).item()
+    e_bs = max(hi - bs, bs - lo, 0.0)
+    out["scale"] = (bs, e_bs)
+    e_u = e_u * bs + (u.abs() + e_u) * e_bs
+    u = u * bs
+    if bs != 1.0 or e_bs != 0.0:
+      e_u = e_u + _rd(u.abs() + e_u)
+  if momentum > 0:
+    m = mom.double().reshape(Bn, R, C)
+    t1, t2 = momentum * m, om * u
+    mn = t1 + t2
+    e_m = _rd(t1) + om * e_u + _rd(t2)
+    e_m = e_m + _rd(mn.abs() + e_m)
+    o = _store(mn, e_m, mom.dtype == BF16)
+    out["mom"] = Out(o.ref.view(B1, B2, R, C), o.bound.view(B1, B2, R, C),
+                     None if o.lo_hi is None else tuple(t.view(B1, B2, R, C) for t in o.lo_hi))
+    u, e_u = mn, e_m
+  pn, e_p, d, e_d = _apply(pd, u, e_u, lr_eff, wd, sched)
+  out["p"] = Out(pn.view(B1, B2, R, C), e_p.view(B1, B2, R, C), None)
+  K = _af_stats_K(total, grid_cap)
+  sp, bp = _sumsq(pn, e_p, K)
+  su, bu = _sumsq(d, e_d, K)
+  out["stats"] = (torch.stack([sp, su]), torch.stack([bp, bu]))
+  return out
+
+
+def check_out(out, o, name, legacy=NO_LEGACY):
+  """A kernel output against an Out of the optimizer models; a bf16 store is held to its bound AND to the interval
+  of bf16 numbers the one round-to-nearest-even can give.  Returns max err / bound."""
+  w = check(out, o.ref, o.bound, legacy, name)
+  if o.lo_hi is not None:
+    check(out, o.ref, torch.zeros_like(o.ref), legacy, name + " (RNE interval)", lo_hi=o.lo_hi, report=False)
+  return w
+
+
+def check_stats(stats, ref, bound, name):
+  """The two fp64 statistics (sum p'^2, sum update^2) against the models' (ref, bound)."""
+  return check(stats.double(), ref, bound, NO_LEGACY, name)
+
+
 # ------------------------------------------------- checkers of the GPU tests ----
 def check_gemm(out, ref, a, b_t, legacy, name, n_adds=1, alpha=1.0):
   """GEMM output (bf16 or fp32 by out's dtype) of A [M][K] @ B^T [K][N] (+ n_adds fp32 epilogue adds) vs the fp64 ref."""
@@ -728,3 +1078,160 @@ def check_ln_edge_launch(ops, x, scale, bias, dys, dres=None, strided=None, idx=
       assert (dxs.view(n, L, D)[:, others] == 0).all(), f"{tag}: strided launch wrote other rows"
       leg = (1e-4, 1e-4) if x.dtype == F32 else (1e-2, 1e-2)
       check_ln_bwd(dxs.view(n, L, D)[:, off], sel, scale, dys_, legacy=leg, name=f"{tag}: strided bwd")
+
+
+def _sl(x, a, b):
+  return x[a:b] if torch.is_tensor(x) and x.dim() > 0 else x
+
+
+def check_chain_step(kind, new, before, lr_eff, wd_eff, sched, gsq, clip_norm, hp, name, legacy=NO_LEGACY,
+                     stats=None, chunk=1 << 20):
+  """One step of the fused chain (kind "adam" | "trace") against adam_bounds / trace_bounds.  new: {"p", "mu" | "trace",
+  "nu"} after the step; before: {"p", "g", "mu" | "trace", "nu"} as stored before it; lr_eff / wd_eff / sched: scalars
+  or per-element fp32 tensors; hp: the remaining hyper-parameters of the model (b1, b2, eps, bc1, bc2 | beta,
+  nesterov).  The model is evaluated in blocks of `chunk` elements.  legacy: {operand: (rtol, atol)} or one pair.
+  Returns {operand: max err / bound}."""
+  n = before["p"].numel()
+  worst, sref, sbnd = {}, 0.0, 0.0
+  for a in range(0, n, chunk):
+    b = min(n, a + chunk)
+    args = (_sl(lr_eff, a, b), _sl(wd_eff, a, b), _sl(sched, a, b), gsq, clip_norm)
+    if kind == "adam":
+      m = adam_bounds(before["p"][a:b], before["g"][a:b], before["mu"][a:b], before["nu"][a:b], *args, **hp)
+    else:
+      tr = before.get("trace")
+      m = trace_bounds(before["p"][a:b], before["g"][a:b], None if tr is None else tr[a:b], *args, **hp)
+    for k, o in m.items():
+      if k == "stats":
+        sref, sbnd = sref + o[0], sbnd + o[1]
+        continue
+      leg = legacy.get(k, NO_LEGACY) if isinstance(legacy, dict) else legacy
+      leg = (leg[0], _sl(leg[1], a, b))          # (the atol may be a per-element tensor)
+      tag = f"{name} {k}" + (f" [{a}:{b}]" if n > chunk else "")
+      worst[k] = max(worst.get(k, 0.0), check_out(new[k][a:b], o, tag, leg))
+  if stats is not None:
+    worst["stats"] = check_stats(stats, sref, sbnd, f"{name} stats")
+  return worst
+
+
+def af_views(bufs, view):
+  """The leaf's [B1][B2][R][C] views of flat buffers, view = (off, B1, B2, R, C, sB1, sB2, sR, sC)."""
+  o, B1, B2, R, C, sB1, sB2, sR, sC = (int(x) for x in view)
+  return [None if t is None else t.as_strided((B1, B2, R, C), (sB1, sB2, sR, sC), o) for t in bufs]
+
+
+def check_af_leaf(new, before, view, factored, gsq, clip_norm, hp, name, legacy=NO_LEGACY, stats=None,
+                  block_rms_clip=0.0, usq=None, grid_cap=2048, model=None):
+  """One Adafactor leaf after a step against adafactor_bounds.  new / before: {"p", "g" (before), "mom", "state"}: flat
+  buffers (p, g, mom) and the leaf's fp32 statistics slice; view: the 9 view numbers; hp: decay, eps, momentum,
+  lr_eff, wd, sched.  Returns ({operand: max err / bound}, model)."""
+  B1, B2, R, C = (int(x) for x in view[1:5])
+  Bn = B1 * B2
+  pv, gv, mv = af_views([before["p"], before["g"], before["mom"]], view)
+  m = model or adafactor_bounds(pv, gv, mv, before["state"], factored, gsq, clip_norm, block_rms_clip=block_rms_clip,
+                                grid_cap=grid_cap, **hp)
+  pn, mn = af_views([new["p"], new["mom"]], view)
+  st = new["state"]
+  worst = {}
+  if factored:
+    parts = {"v_row": st[:Bn * R].view(Bn, R), "v_col": st[Bn * R:Bn * R + Bn * C].view(Bn, C),
+             "rcm": st[Bn * R + Bn * C:Bn * R + Bn * C + Bn]}
+  else:
+    parts = {"v": st[:Bn * R * C].view(B1, B2, R, C)}
+  parts["p"] = pn
+  if "mom" in m:
+    parts["mom"] = mn
+  for k, t in parts.items():
+    leg = legacy.get(k, NO_LEGACY) if isinstance(legacy, dict) else legacy
+    worst[k] = check_out(t, m[k], f"{name} {k}", leg)
+  if stats is not None:
+    worst["stats"] = check_stats(stats, m["stats"][0], m["stats"][1], f"{name} stats")
+  if usq is not None and "usq" in m:
+    worst["usq"] = check(usq, m["usq"][0], m["usq"][1], NO_LEGACY, f"{name} usq")
+  return worst, m
+
+
+# ---- a whole optimizer object (big_vision_amd.optax.Chain / Adafactor on one rank): the step it just made, per
+# element, from the buffers it held before the step
+def snapshot_opt(opt):
+  """The buffers an optimizer step reads and overwrites, cloned before the step (the gradient buffer is not cloned:
+  the step leaves it as it is and may be filled after this call)."""
+  st = opt.store
+  n = st.trainable_count
+  snap = dict(p=st.master[:n].clone(), mu=None if getattr(opt, "mu", None) is None else opt.mu.clone())
+  if getattr(opt, "nu", None) is not None:
+    snap["nu"] = opt.nu.clone()
+  if getattr(opt, "af_state", None) is not None:
+    snap["state"] = opt.af_state.clone()
+  return snap
+
+
+def _entry_atol(st, p_before, p_after, r):
+  """The max-normalised legacy tolerance r max(1, max|p| of the store entry) as a per-element atol."""
+  n = st.trainable_count
+  atol = torch.full((n,), r, dtype=F64, device=p_before.device)
+  for e in st.entries.values():
+    if e.name not in st.frozen and e.offset + e.numel <= n:
+      sl = slice(e.offset, e.offset + e.numel)
+      atol[sl] = r * max(1.0, p_after[sl].abs().max().item())
+  return atol
+
+
+def check_opt_step(opt, snap, name, legacy_p=2e-6, legacy_state=2e-5, legacy_state_bf16=1e-2):
+  """The step `opt` made since snapshot_opt, operand by operand and element by element, against the chain / Adafactor
+  models evaluated on the snapshot, this step's gradient buffer, gsq and schedule values.  legacy_*: the
+  max-normalised tolerances of the fixture assertions (r max(1, max|p|) per store entry or Adafactor leaf for the
+  parameters, r max|state| for an accumulator), which cap the model bounds.  Returns {operand: max err / bound}."""
+  st = opt.store
+  n = st.trainable_count
+  assert not opt.sharded
+  k = opt.count - 1
+  sched = [f32s(fn(k)) for fn in opt.schedule_fns]
+  gsq, clip_norm = opt.gsq.item(), float(opt.clip_norm or 0.0)
+  p, g = st.master[:n], st.grad[:n]
+  acc_leg = lambda t: (0.0, (legacy_state_bf16 if t.dtype == BF16 else legacy_state) * max(1e-30, t.double().abs().max().item()))
+  if opt.kind in ("adam", "trace", "identity"):
+    cs = opt.chunk_seg.long()[:n // 1024]
+    el = lambda col: col[cs].repeat_interleave(1024)
+    lr_t, wd_t = el(opt.segs[:, 0]), el(opt.segs[:, 1])
+    si = el(opt.segs[:, 2].contiguous().view(torch.int32)).long()
+    sc_t = torch.tensor(sched + [0.0] * (8 - len(sched)), dtype=F32, device=p.device)[si]
+    leg = {"p": (0.0, _entry_atol(st, snap["p"], p, legacy_p))}
+    if opt.kind == "adam":
+      before = dict(p=snap["p"], g=g, mu=snap["mu"][:n], nu=snap["nu"][:n])
+      new = dict(p=p, mu=opt.mu[:n], nu=opt.nu[:n])
+      hp = dict(b1=opt.b1, b2=opt.b2, eps=opt.eps, bc1=1.0 - opt.b1 ** (k + 1), bc2=1.0 - opt.b2 ** (k + 1))
+      leg["mu"], leg["nu"] = acc_leg(new["mu"]), acc_leg(new["nu"])
+    else:
+      tr = None if opt.kind == "identity" else snap["mu"][:n]
+      before = dict(p=snap["p"], g=g, trace=tr)
+      new = dict(p=p, trace=None if tr is None else opt.mu[:n])
+      hp = dict(beta=opt.momentum, nesterov=opt.nesterov)
+      if tr is not None:
+        leg["trace"] = acc_leg(new["trace"])
+    return check_chain_step("adam" if opt.kind == "adam" else "trace", new, before, lr_t, wd_t, sc_t, gsq, clip_norm, hp,
+                            name, legacy=leg, stats=opt.stats)
+  af = opt.af
+  t = float(k - af["decay_offset"]) + 1.0
+  decay = min(af["beta2_cap"], 1.0 - t ** (-af["decay_rate"]))
+  worst, sref, sbnd = {}, 0.0, 0.0
+  for lf in opt.af_leaves:
+    sl = slice(lf["soff"], lf["soff"] + lf["n_state"])
+    hp = dict(decay=decay, eps=af["eps"], momentum=af["momentum"], lr_eff=lf["lr_eff"], wd=lf["wd"],
+              sched=sched[lf["sched"]])
+    pv = af_views([p], lf["view"])[0]
+    leg = {"p": (0.0, legacy_p * max(1.0, pv.abs().max().item()))}
+    if opt.mu is not None:
+      leg["mom"] = acc_leg(af_views([opt.mu], lf["view"])[0])
+    br, bc = lf["B"] * lf["R"], lf["B"] * lf["C"]
+    for key, a, b in ((("v_row", 0, br), ("v_col", br, br + bc)) if lf["factored"] else (("v", 0, lf["n_state"]),)):
+      leg[key] = acc_leg(opt.af_state[sl][a:b])
+    w, m = check_af_leaf(dict(p=p, mom=opt.mu, state=opt.af_state[sl]),
+                         dict(p=snap["p"], g=g, mom=snap["mu"], state=snap["state"][sl]), lf["view"], lf["factored"], gsq,
+                         clip_norm, hp, f"{name} {lf['leaf']}", legacy=leg, block_rms_clip=af["block_rms_clip"],
+                         grid_cap=1024)
+    for kk, v in w.items():
+      worst[kk] = max(worst.get(kk, 0.0), v)
+    sref, sbnd = sref + m["stats"][0], sbnd + m["stats"][1]
+  worst["stats"] = check_stats(opt.stats, sref, sbnd, f"{name} stats")
+  return worst

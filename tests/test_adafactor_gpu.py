@@ -8,6 +8,8 @@ import math
 import pytest
 import torch
 
+import _bounds as B
+
 pytestmark = pytest.mark.gpu
 
 
@@ -50,8 +52,12 @@ def _two_steps(dev, frozen, clip, mom="bfloat16"):
   batch = {"image": image.to(dev), "labels": text.to(dev)}
   for step in range(2):
     p_before = snap(state["params"])
+    before = B.snapshot_opt(state["opt"])
     state, meas = update_fn(state, None, batch)
     torch.cuda.synchronize()
+    # every leaf per element (statistics, momentum, parameters) from the state the kernels stored before the step, on
+    # the step's own gradient buffer (tests/_bounds.py adafactor_bounds); 2e-5 max(1, max|p|) caps the parameter bound
+    B.check_opt_step(state["opt"], before, f"adafactor two towers step {step}", legacy_p=2e-5)
     gours = snap(store.tree("grad"))
     g_all = {k: gours.get(k, torch.zeros_like(v)) for k, v in p_before.items()}
     # the oracle runs in fp32 like the kernel (the bf16 momentum makes fp64 vs fp32 a different function)

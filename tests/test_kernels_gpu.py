@@ -835,10 +835,16 @@ def test_sqnorm_and_adam_vs_oracle(dev):
     ops.sqnorm_(gd, gsq)
     assert_close(gsq.cpu()[0], (gk.double() ** 2).sum(), 1e-6, 0, "sqnorm")
     stats = torch.zeros(2, device=dev, dtype=torch.float64)
+    before = dict(p=p.clone(), g=gd, mu=mu.clone(), nu=nu.clone())
     ops.adam_step_(p, gd, mu, nu, shadow, segs, chunk_seg, count, [sched], gsq, 1.0, 0.9, 0.999, 1e-8,
                    1 - 0.9 ** (k + 1), 1 - 0.999 ** (k + 1), stats)
     ref = torch.cat([params["a"]["kernel"], params["a"]["bias"]])
     assert_close(p.cpu(), ref, 1e-5, 1e-6, f"adam params step {k}")
+    # per element, p, mu and nu of THIS step from the state the kernel stored before it (tests/_bounds.py adam_bounds)
+    wd_t = torch.cat([torch.full((3072,), cfg["wd"]), torch.zeros(1024)]).to(dev)
+    B.check_chain_step("adam", dict(p=p, mu=mu, nu=nu), before, B.f32s(cfg["lr"]), wd_t, B.f32s(sched), gsq.item(), 1.0,
+                       dict(b1=0.9, b2=0.999, eps=1e-8, bc1=1 - 0.9 ** (k + 1), bc2=1 - 0.999 ** (k + 1)),
+                       f"adam vs oracle inputs, step {k}", legacy=(1e-5, 1e-6), stats=stats)
     assert torch.equal(shadow, p.to(BF16))
     assert_close(stats.cpu()[0], (ref ** 2).sum(), 1e-5, 0, "l2_params^2")
     u = torch.cat([upd["a"]["kernel"], upd["a"]["bias"]])

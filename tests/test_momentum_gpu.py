@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+import _bounds as B
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -50,9 +52,13 @@ def test_momentum_follows_the_executed_reference(dev, fixture):
     for n in names:
       if n not in frozen:
         store.leaf(n, "grad").copy_(torch.from_numpy(np.asarray(z[f"grad/{step}/{n}"], np.float32)))
+    snap = B.snapshot_opt(opt)
     opt.step()
     torch.cuda.synchronize()
     assert bv_optax.get_count(opt) == step + 1
+    # this step per element (parameters, accumulators, statistics) from the state the kernel stored before it, on the
+    # fixture's gradients and configuration (tests/_bounds.py); the fixture tolerances below cap the model bounds
+    B.check_opt_step(opt, snap, f"{fixture} step {step}")
     for n in names:
       upd = np.asarray(z[f"update/{step}/{n}"], np.float64)
       ref[n] = ref[n] + upd

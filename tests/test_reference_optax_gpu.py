@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import _bounds as B
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import run_reference_optax as RO  # noqa: E402  (case tables only)
@@ -50,9 +52,13 @@ def test_product_optimizer_follows_the_executed_reference(dev, name):
     for n in names:
       if n not in frozen:
         store.leaf(n, "grad").copy_(torch.from_numpy(np.asarray(z[f"grad/{step}/{n}"], np.float32)))
+    snap = B.snapshot_opt(opt)
     opt.step()
     torch.cuda.synchronize()
     assert bv_optax.get_count(opt) == step + 1
+    # this step per element (parameters, accumulators, statistics) from the state the kernel stored before it, on the
+    # fixture's gradients and configuration (tests/_bounds.py); the fixture tolerances below cap the model bounds
+    B.check_opt_step(opt, snap, f"{name} step {step}")
     for n in names:
       upd = np.asarray(z[f"update/{step}/{n}"], np.float64)
       ref[n] = ref[n] + upd

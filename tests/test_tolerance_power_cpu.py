@@ -641,3 +641,398 @@ def test_loss_bounds_bite_on_extreme_rows():
   naive = torch.log(1 + torch.exp(-x)).sum() / Bn
   accept("siglip", "SigLIP loss: max(-x, 0) + log1p(exp(-|x|))", stable.reshape(1), ref.reshape(1), one, (1e-5, 1e-6))
   reject("siglip", "naive log(1 + exp(-x))", naive.reshape(1), ref.reshape(1), one, (1e-5, 1e-6))
+
+
+# ------------------------------------------------------------- optimizer ----
+# fp32 emulations of loss_optim.hip opt_chain and adafactor.hip with the signatures of big_vision_amd.ops: the same
+# order of operations, fp32 intermediates, bf16 stores by round-to-nearest-even.  `slip` makes one catalogued mistake.
+import types
+
+import numpy as np
+
+import _opt_cases as OC
+
+f32 = np.float32
+
+
+def _clip32(gsq, clip_norm, slip=None):
+  cn = f32(clip_norm or 0.0)
+  if not cn > 0:
+    return 1.0
+  gn = f32(np.sqrt(np.float64(gsq.item())))
+  if slip == "clip applied unconditionally":
+    return float(cn / gn) if gn > 0 else 1.0
+  return float(cn / gn) if gn > cn else 1.0
+
+
+def _store(buf, val, slip, what):
+  if buf.dtype == BF16:
+    buf.copy_((trunc(val) if slip == f"{what} stored by truncation" else rne(val)).to(BF16))
+  else:
+    buf.copy_(val)
+
+
+def _one_minus(b):
+  return float(f32(1) - f32(b))
+
+
+def emu_chain(kind, p, g, acc, nu, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, stats, slip=None, b1=0, b2=0,
+              eps=0, bc1=1, bc2=1, beta=0, nesterov=False, k=None):
+  arr = segs.numpy().view(OC.SEG)
+  cs = chunk_seg.long()
+  el = lambda a: torch.from_numpy(np.ascontiguousarray(a))[cs].repeat_interleave(1024)
+  lr, wd, si = el(arr["lr"]), el(arr["wd"]), el(arr["si"]).long()
+  if slip == "a segment's sched_idx off by one":
+    si = (si + 1) % OC.MAX_SCHED
+  sc = torch.tensor([float(f32(v)) for v in sched] + [0.0] * (OC.MAX_SCHED - len(sched)), dtype=F32)[si]
+  clip = _clip32(gsq, clip_norm, slip)
+  late = slip == "clip applied after the moments"
+  gc = g * clip if not late else g.clone()
+  pv = p.clone()
+  if slip == "weight decay coupled into g before the moments":
+    gc = gc + wd * pv
+  if kind == "adam":
+    b1, b2, eps, bc1, bc2 = (float(f32(x)) for x in (b1, b2, eps, bc1, bc2))
+    if slip == "bc computed for step k rather than k + 1":
+      bc1, bc2 = float(f32(1 - b1 ** k)), float(f32(1 - b2 ** k))
+    m = b1 * acc.float() + _one_minus(b1) * gc
+    gv = g if slip == "nu updated with the unclipped g" else gc
+    v = b2 * nu + _one_minus(b2) * gv * gv
+    mm = rne(m) if slip == "update formed from the bf16-rounded mu" else m
+    if late:
+      mm = mm * clip
+    mh = mm if slip == "bias correction of mu omitted" else mm / bc1
+    vh = v if slip == "bias correction of nu omitted" else v / bc2
+    if slip == "eps inside the square root":
+      u = mh / torch.sqrt(vh + eps)
+    elif slip == "eps added before the bc2 division":
+      u = mh / torch.sqrt((v + eps) / bc2)
+    else:
+      u = mh / (torch.sqrt(vh) + eps)
+    nu.copy_(v)
+    _store(acc, m, slip, "mu")
+  elif kind == "trace":
+    beta = float(f32(beta))
+    t = gc + beta * acc.float()
+    if nesterov:
+      tt = rne(t) if slip == "Nesterov from the rounded t'" else t
+      u = gc + beta * (acc.float() if slip == "Nesterov as g + beta t_old" else tt)
+    else:
+      u = rne(t) if slip == "update formed from the bf16-rounded mu" else t
+    if late:
+      u = u * clip
+    _store(acc, t, slip, "mu")
+  else:
+    u = gc * (clip if late else 1.0)
+  if slip == "weight decay coupled into g before the moments":
+    d = (lr * u) * sc
+  elif slip == "weight decay not multiplied by the schedule":
+    d = (lr * u) * sc + wd * pv
+  else:
+    d = (lr * u + wd * pv) * sc
+  p.copy_(pv - d)
+  shadow.copy_(p.to(BF16))
+  if stats is not None:
+    stats += torch.stack([(p.double() ** 2).sum(), (d.double() ** 2).sum()])
+
+
+def _af_leaf_emu(p, g, mom, shadow, view, st, factored, clip, decay, eps, momentum, lr_eff, wd, sched, stats, slip=None,
+                 usq_out=None, block_rms_clip=0.0):
+  o, B1, B2, R, C = (int(x) for x in view[:5])
+  Bn = B1 * B2
+  pv, gv, mv, sv = B.af_views([p, g, mom, shadow], view)
+  x = (gv * clip).reshape(Bn, R, C)
+  xs = gv.reshape(Bn, R, C) if slip == "statistics formed from the unclipped gradient" else x
+  decay, momentum = float(f32(decay)), float(f32(momentum))
+  e = 0.0 if slip == "eps omitted" else float(f32(eps))
+  od, om = _one_minus(decay), _one_minus(momentum)
+  if factored:
+    v_row, v_col = st[:Bn * R].view(Bn, R), st[Bn * R:Bn * R + Bn * C].view(Bn, C)
+    rcm = st[Bn * R + Bn * C:Bn * R + Bn * C + Bn]
+    sq = xs * xs + e
+    nC = R if slip == "the mean divided by the wrong extent (R for C)" else C
+    v_row.copy_(decay * v_row + od * (sq.sum(2) / nC))
+    v_col.copy_(decay * v_col + od * (sq.sum(1) / R))
+    rcm.copy_(v_row.sum(1) / R)
+    if slip == "row and column factors exchanged":
+      assert R == C
+      rf, cf = torch.rsqrt(v_col / rcm[:, None]), torch.rsqrt(v_row)
+    elif slip == "row and column factors exchanged (R != C)":   # v_col read with the row index, v_row with the column's
+      ci = torch.arange(C).clamp_max(R - 1)
+      rf, cf = torch.rsqrt(v_col[:, torch.arange(R).clamp_max(C - 1)] / rcm[:, None]), torch.rsqrt(v_row[:, ci])
+    elif slip == "row and column factors exchanged (rcm divides v_col)":
+      rf, cf = torch.rsqrt(v_row), torch.rsqrt(v_col / rcm[:, None])
+    elif slip == "rcm omitted":
+      rf, cf = torch.rsqrt(v_row), torch.rsqrt(v_col)
+    else:
+      rf, cf = torch.rsqrt(v_row / rcm[:, None]), torch.rsqrt(v_col)
+    u = x * rf[:, :, None] * cf[:, None, :]
+  else:
+    v = st[:Bn * R * C].view(Bn, R, C)
+    v.copy_(decay * v + od * (xs * xs + e))
+    u = x * torch.rsqrt(v)
+  if block_rms_clip > 0:
+    if slip == "block_rms_clip's rms taken per batch slice instead of per leaf":
+      usq = (u.double() ** 2).sum((1, 2), keepdim=True)
+      rms = torch.sqrt((usq / (R * C)).float())
+    else:
+      usq = (u.double() ** 2).sum()
+      rms = torch.sqrt((usq / (Bn * R * C)).float())
+    if usq_out is not None:
+      usq_out.copy_(usq.sum())
+    u = u * (1.0 / torch.clamp_min(rms / float(f32(block_rms_clip)), 1.0))
+  if momentum > 0:
+    m = momentum * mv.float().reshape(Bn, R, C) + (u if slip == "(1 - momentum) missing" else om * u)
+    mst = trunc(m) if slip == "momentum stored by truncation" else rne(m)
+    mv.copy_((mst if mom.dtype == BF16 else m).view(B1, B2, R, C).to(mom.dtype))
+    um = rne(m) if slip == "update formed from the bf16-rounded momentum" else m
+  else:
+    um = u
+  pd = pv.reshape(Bn, R, C).clone()
+  w = (lr_eff * wd) if slip == "weight decay multiplied by lr_eff" else wd
+  upd = -float(f32(sched)) * (float(f32(lr_eff)) * um + float(f32(w)) * pd)
+  pn = pd + upd
+  pv.copy_(pn.view(B1, B2, R, C))
+  sv.copy_(pv.to(BF16))
+  if stats is not None:
+    stats += torch.stack([(pn.double() ** 2).sum(), (upd.double() ** 2).sum()])
+
+
+def make_emu(slip=None):
+  def adam_step_(p, g, mu, nu, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, b1, b2, eps, bc1, bc2, stats):
+    k = round(math.log(1 - bc1) / math.log(b1)) - 1
+    emu_chain("adam", p, g, mu, nu, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, stats, slip, b1=b1, b2=b2,
+              eps=eps, bc1=bc1, bc2=bc2, k=k)
+
+  def trace_step_(p, g, trace, shadow, segs, chunk_seg, count, sched, gsq, clip_norm, momentum, nesterov, stats):
+    emu_chain("trace" if trace is not None else "identity", p, g, trace, None, shadow, segs, chunk_seg, count, sched, gsq,
+              clip_norm, stats, slip, beta=momentum, nesterov=nesterov)
+
+  def sqnorm_(x, out):
+    out += (x.float() * x.float()).double().sum()
+
+  def adafactor_leaf_(p, g, mom, shadow, view, state, factored, gsq, clip_norm, decay, eps, m, lr_eff, wd, sched, stats):
+    if slip == "decay of step k + 1 at step k":
+      decay = OC.af_decay(round((1 - decay) ** (-1 / 0.8)))
+    _af_leaf_emu(p, g, mom, shadow, list(view), state, factored, _clip32(gsq, clip_norm), decay, eps, m, lr_eff, wd,
+                 sched, stats, slip)
+
+  def adafactor_step_(p, g, mom, shadow, leaves, nleaves, max_rows, max_cols, max_b, max_total, state, gsq, clip_norm,
+                      decay, eps, m, sched, stats, block_rms_clip=0.0, block_usq=None):
+    from big_vision_amd import optax as bvo
+    tab = leaves.numpy().reshape(-1).view(bvo.AF_LEAF)
+    for j in range(nleaves):
+      L = tab[j]
+      view = [int(L[n]) for n in ("off", "B1", "B2", "R", "C", "sB1", "sB2", "sR", "sC")]
+      Bn = view[1] * view[2]
+      n_state = Bn * (view[3] + view[4] + 1) if L["factored"] else Bn * view[3] * view[4]
+      _af_leaf_emu(p, g, mom, shadow, view, state[int(L["soff"]):int(L["soff"]) + n_state], bool(L["factored"]),
+                   _clip32(gsq, clip_norm), decay, eps, m, float(L["lr_eff"]), float(L["wd"]), sched[int(L["sched_idx"])],
+                   stats, slip, usq_out=None if block_usq is None else block_usq[j], block_rms_clip=block_rms_clip)
+  return types.SimpleNamespace(adam_step_=adam_step_, trace_step_=trace_step_, sqnorm_=sqnorm_,
+                               adafactor_leaf_=adafactor_leaf_, adafactor_step_=adafactor_step_)
+
+
+EMU = make_emu()
+
+
+def _accepted(worst, family):
+  for k, v in worst.items():
+    _rec(family, f"ACCEPT {k}: max err/bound {v:.3f}", 0, 1)
+    assert v <= 1.0
+
+
+@pytest.mark.parametrize("mu", [F32, BF16])
+@pytest.mark.parametrize("clip", [0.0, 1e-2])
+@pytest.mark.parametrize("nchunks,nseg", [(1, 1), (3, 3), (8, 2)])
+def test_adam_model_accepts_the_emulation(nchunks, nseg, clip, mu):
+  """The drivers of the GPU file on the fp32 emulation (the 4099-chunk case at 8 chunks: the same alternating segment
+  pattern; the grid-stride loop is the kernel's own matter)."""
+  _accepted(OC.chain_case(EMU, CPU, "adam", nchunks, nseg, clip, mu), "adam")
+
+
+@pytest.mark.parametrize("kind,nesterov,dt", [("trace", False, BF16), ("trace", False, F32), ("trace", True, BF16),
+                                              ("trace", True, F32), ("identity", False, None)])
+def test_trace_model_accepts_the_emulation(kind, nesterov, dt):
+  _accepted(OC.chain_case(EMU, CPU, kind, 2, 2, 1e-2, dt, nesterov=nesterov), "trace")
+
+
+@pytest.mark.parametrize("which", ["zero", "at", "ulp-above", "far"])
+def test_clip_threshold_model_accepts_the_emulation(which):
+  for kind in ("adam", "trace"):
+    _accepted(OC.chain_case(EMU, CPU, kind, 1, 1, 0.5, F32, gsq_value=OC.clip_gsq(which, 0.5)), "clip")
+  _accepted(OC.af_leaf_case(EMU, CPU, B.AF_SPECS[0], BF16, 0.5, gsq_value=OC.clip_gsq(which, 0.5)), "clip")
+  c, e = B.clip_factor(OC.clip_gsq(which, 0.5), 0.5)
+  assert (c == 1.0 and e == 0.0) == (which in ("zero", "at")), (which, c)
+
+
+@pytest.mark.parametrize("mom", [BF16, F32])
+@pytest.mark.parametrize("spec", B.AF_SPECS, ids=[s[0] for s in B.AF_SPECS])
+def test_adafactor_model_accepts_the_emulation(spec, mom):
+  _accepted(OC.af_leaf_case(EMU, CPU, spec, mom, 1e-2), "adafactor")
+
+
+@pytest.mark.parametrize("mom", [BF16, F32])
+@pytest.mark.parametrize("single", [False, True])
+@pytest.mark.parametrize("brc", [0.0, 0.7, 1e6])
+def test_adafactor_batched_model_accepts_the_emulation(brc, single, mom):
+  _accepted(OC.af_batched_case(EMU, CPU, mom, brc, single), "adafactor")
+
+
+def test_sqnorm_model_accepts_the_emulation():
+  for count in (1, 3, 4, 5, 1023, 1024 * 257 + 3, 2048 * 256 * 4 + 4 * 256 + 1):
+    _accepted(OC.sqnorm_case(EMU, CPU, count), "sqnorm")
+  _accepted(OC.sqnorm_case(EMU, CPU, 1023, offset=4), "sqnorm")
+
+
+# ---- rejection: one step of the emulation with one slip, on the GPU cases' inputs, three seeds.  Each line prints the
+# elements the model (capped at the legacy tolerance) rejects, then the elements the legacy tolerance alone rejects.
+# Legacy tolerances: p (1e-5, 1e-6) for the chain (test_kernels_gpu.py), 2e-5 max(1, max|p|) for Adafactor
+# (test_adafactor_gpu.py); state 2e-5 of the leaf's largest state value, 1e-2 when the accumulator is bf16.
+SEEDS = (100, 1100, 2100)
+# Slips recorded as not separable from rounding.  Exchanging WHICH factor carries rcm, (x rsqrt(v_row)) rsqrt(v_col /
+# rcm), is the same product in exact arithmetic (on any leaf, and by symmetry on an R = C leaf in particular): only
+# roundings differ, no elementwise bound can tell.  The exchange that reads v_col with the row index and v_row with
+# the column index is a different slip, rejected on R != C and on R = C leaves alike, and has lines of its own.
+NOT_SEPARABLE = {"adafactor": ["row and column factors exchanged (rcm divides v_col)"], "adam": [], "trace": []}
+
+
+def _legacy_of(k, o, out, family):
+  mx = o.ref.abs().max().item()
+  if k == "p":
+    return (1e-5, 1e-6) if family != "adafactor" else (0.0, 2e-5 * max(1.0, mx))
+  return (0.0, (1e-2 if out.dtype == BF16 else 2e-5) * mx)
+
+
+def _count(outs, m, family):
+  nm = nl = tot = 0
+  for k, o in m.items():
+    if k in ("stats", "usq", "scale"):
+      continue
+    out = outs[k].reshape(o.ref.shape)
+    leg = _legacy_of(k, o, out, family)
+    a = B.count_rejected(out, o.ref, o.bound, leg)
+    if o.lo_hi is not None:
+      a = max(a, B.count_rejected(out, o.ref, torch.zeros_like(o.ref), None, o.lo_hi))
+    nm += a
+    nl += B.count_rejected(out, o.ref, leg[1] + leg[0] * o.ref.abs())
+    tot += out.numel()
+  return nm, nl, tot
+
+
+def _slip_line(family, slip, counts, separable=True):
+  nm = [c[0] for c in counts]; nl = [c[1] for c in counts]
+  print(f"[power] {family:10s} {slip:62s} model rejects {nm} / {counts[0][2]}, legacy tolerance alone {nl}"
+        + ("" if separable else "   (recorded, not separable)"))
+  ROWS.append((family, slip, min(nm), counts[0][2]))
+  if separable:
+    assert min(nm) > 0, f"{family}: slip '{slip}' passes the model in a seed: {nm}"
+
+
+def _chain_slip(kind, slip, seed, nesterov=False):
+  n, count = 3, 3 * 1024
+  segs, chunk_seg, lr_t, wd_t, si_t = OC.seg_setup(n, 3, CPU)
+  p, _ = B.opt_inputs(count, CPU, seed)
+  acc = B.rnd((count,), CPU, seed + 2, 1e-3).to(BF16)
+  nu = B.rnd((count,), CPU, seed + 3, 1e-3) ** 2
+  _, g = B.opt_inputs(count, CPU, seed + 10)
+  gsq = (g.double() ** 2).sum().reshape(1)
+  clip_norm = 0.5 * math.sqrt(gsq.item()) if slip != "clip applied unconditionally" else 2.0 * math.sqrt(gsq.item())
+  k = OC.STEPS[0]
+  sc_t = torch.tensor(OC.SCHED[0], dtype=F32)[si_t]
+  before = dict(p=p.clone(), g=g, mu=acc.clone(), nu=nu.clone(), trace=acc.clone())
+  shadow = torch.empty(count, dtype=BF16)
+  if kind == "adam":
+    hp = dict(OC.ADAM, bc1=1 - 0.9 ** (k + 1), bc2=1 - 0.999 ** (k + 1))
+    emu_chain("adam", p, g, acc, nu, shadow, segs, chunk_seg, count, OC.SCHED[0], gsq, clip_norm, None, slip, k=k, **hp)
+    m = B.adam_bounds(before["p"], g, before["mu"], before["nu"], lr_t, wd_t, sc_t, gsq.item(), clip_norm, **hp)
+    return _count(dict(p=p, mu=acc, nu=nu), m, "adam")
+  emu_chain("trace", p, g, acc, None, shadow, segs, chunk_seg, count, OC.SCHED[0], gsq, clip_norm, None, slip, beta=0.9,
+            nesterov=nesterov)
+  m = B.trace_bounds(before["p"], g, before["trace"], lr_t, wd_t, sc_t, gsq.item(), clip_norm, 0.9, nesterov)
+  return _count(dict(p=p, trace=acc), m, "trace")
+
+
+ADAM_SLIPS = ["eps inside the square root", "eps added before the bc2 division", "bias correction of mu omitted",
+              "bias correction of nu omitted", "bc computed for step k rather than k + 1",
+              "weight decay not multiplied by the schedule", "weight decay coupled into g before the moments",
+              "clip applied unconditionally", "clip applied after the moments", "nu updated with the unclipped g",
+              "mu stored by truncation", "update formed from the bf16-rounded mu", "a segment's sched_idx off by one"]
+TRACE_SLIPS = [("Nesterov from the rounded t'", True), ("Nesterov as g + beta t_old", True),
+               ("mu stored by truncation", False), ("update formed from the bf16-rounded mu", False),
+               ("clip applied unconditionally", True), ("clip applied after the moments", False),
+               ("weight decay not multiplied by the schedule", True), ("a segment's sched_idx off by one", False)]
+
+
+def test_adam_and_trace_bounds_bite():
+  assert _chain_slip("adam", None, 100)[0] == 0 and _chain_slip("trace", None, 100, True)[0] == 0
+  for slip in ADAM_SLIPS:
+    _slip_line("adam", slip, [_chain_slip("adam", slip, s) for s in SEEDS])
+  for slip, nest in TRACE_SLIPS:
+    _slip_line("trace", slip + (" (nesterov)" if nest else ""), [_chain_slip("trace", slip, s, nest) for s in SEEDS])
+  assert len(NOT_SEPARABLE["adam"]) <= 2 and len(NOT_SEPARABLE["trace"]) <= 2
+
+
+def _af_slip(slip, leaf, seed, brc=0.0, want_nonfinite=False):
+  spec = next(s for s in B.AF_SPECS if s[0] == leaf)
+  lf = OC.af_leaf_record(spec, seed, CPU)
+  p, g, state, view = lf["p"], lf["g"], lf["state"], list(lf["view"])
+  n = p.numel()
+  mom = B.rnd((n,), CPU, seed + 5, 0.3).to(BF16)
+  shadow = torch.zeros(n, dtype=BF16)
+  gsq = (g.double() ** 2).sum().reshape(1)
+  clip_norm = 0.5 * math.sqrt(gsq.item())
+  k = OC.STEPS[0]
+  decay = OC.af_decay(k)
+  hp = dict(OC.AF, decay=decay, lr_eff=lf["lr_eff"], wd=lf["wd"], sched=OC.SCHED[0][0])
+  before = dict(p=p.clone(), mom=mom.clone(), state=state.clone())
+  _af_leaf_emu(p, g, mom, shadow, view, state, lf["factored"], _clip32(gsq, clip_norm),
+               OC.af_decay(k + 1) if slip == "decay of step k + 1 at step k" else decay, 1e-30, 0.9, lf["lr_eff"],
+               lf["wd"], hp["sched"], None, slip, block_rms_clip=brc)
+  pv, gv, mv = B.af_views([before["p"], g, before["mom"]], view)
+  m = B.adafactor_bounds(pv, gv, mv, before["state"], lf["factored"], gsq.item(), clip_norm, block_rms_clip=brc, **hp)
+  Bn, R, C = lf["B"], lf["R"], lf["C"]
+  pn, mn = B.af_views([p, mom], view)
+  outs = dict(p=pn, mom=mn, v_row=state[:Bn * R], v_col=state[Bn * R:Bn * R + Bn * C],
+              rcm=state[Bn * R + Bn * C:Bn * R + Bn * C + Bn], v=state[:Bn * R * C])
+  if want_nonfinite:
+    assert not bool(torch.isfinite(pn).all()), "eps omitted: the zero-gradient row should give a non-finite update"
+  return _count(outs, m, "adafactor")
+
+
+AF_SLIPS = [("rcm omitted", "2x3x32x40-padded", 0.0), ("statistics formed from the unclipped gradient", "2x3x32x40-padded", 0.0),
+            ("the mean divided by the wrong extent (R for C)", "2x3x32x40-padded", 0.0),
+            ("(1 - momentum) missing", "2x3x32x40-padded", 0.0),
+            ("update formed from the bf16-rounded momentum", "2x3x32x40-padded", 0.0),
+            ("momentum stored by truncation", "2x3x32x40-padded", 0.0),
+            ("weight decay multiplied by lr_eff", "2x3x32x40-padded", 0.0),
+            ("block_rms_clip's rms taken per batch slice instead of per leaf", "2x3x32x40-padded", 0.7),
+            ("decay of step k + 1 at step k", "2x3x32x40-padded", 0.0),
+            ("decay of step k + 1 at step k", "31x500", 0.0), ("statistics formed from the unclipped gradient", "257", 0.0)]
+
+
+def test_adafactor_bounds_bite():
+  for leaf, brc in (("2x3x32x40-padded", 0.0), ("2x3x32x40-padded", 0.7), ("64x64", 0.0), ("31x500", 0.0)):
+    assert _af_slip(None, leaf, 100, brc)[0] == 0, leaf
+  for slip, leaf, brc in AF_SLIPS:
+    _slip_line("adafactor", f"{slip} [{leaf}]", [_af_slip(slip, leaf, s, brc) for s in SEEDS])
+  _slip_line("adafactor", "eps omitted [40x48-zero-row-col: non-finite]",
+             [_af_slip("eps omitted", "40x48-zero-row-col", s, want_nonfinite=True) for s in SEEDS])
+  _slip_line("adafactor", "row and column factors exchanged [32x33]",
+             [_af_slip("row and column factors exchanged (R != C)", "32x33", s) for s in SEEDS])
+  _slip_line("adafactor", "row and column factors exchanged [64x64, R = C]",
+             [_af_slip("row and column factors exchanged", "64x64", s) for s in SEEDS])
+  for slip in NOT_SEPARABLE["adafactor"]:
+    _slip_line("adafactor", f"{slip} [64x64, R = C]", [_af_slip(slip, "64x64", s) for s in SEEDS], separable=False)
+  assert len(NOT_SEPARABLE["adafactor"]) <= 2
+
+
+def test_gpu_checker_calls_name_the_operand():
+  """The GPU file's own checker calls (the drivers of _opt_cases.py) reject an emulated slip with the operand named:
+  one slip each for Adam, trace and Adafactor."""
+  with pytest.raises(AssertionError, match=r"adam .* p:"):
+    OC.chain_case(make_emu("eps inside the square root"), CPU, "adam", 3, 3, 1e-2, F32)
+  with pytest.raises(AssertionError, match=r"trace .* p:"):
+    OC.chain_case(make_emu("Nesterov from the rounded t'"), CPU, "trace", 2, 2, 1e-2, BF16, nesterov=True)
+  with pytest.raises(AssertionError, match=r"adafactor leaf 2x3x32x40-padded .* (p|mom):"):
+    OC.af_leaf_case(make_emu("rcm omitted"), CPU, next(s for s in B.AF_SPECS if s[0] == "2x3x32x40-padded"), BF16, 1e-2)

@@ -6,11 +6,11 @@
 //   q = q / sqrt(Dh);  S = q k^T;  P = softmax_rows(S);  O = P v
 // per (sample, head); no bias, no dropout on this path; optional key-padding lengths (NaFlex, BERT).
 //
-// The kernels live in attention3.hip (forward; two-launch backward for masked sequences and L > 208) and
-// attention5.hip (the backward in one launch for the step's shapes); this file validates arguments, dispatches
-// and holds the MAP head's kernels (models/vit.py:176-178: ONE query per sample and head, a wave per pair).
+// The kernels live in attention3.hip (forward; two-launch backward) and attention5.hip (the backward in one launch
+// for the step's shapes); attn_route.h decides which one serves a call.  This file validates arguments and holds the MAP head's kernels (models/vit.py:176-178: ONE query per sample and head, a wave per pair).
 // Rounds 1-3 also kept a general global-memory kernel set and the first LDS-resident set (attention2.hip) behind
 // A/B switches; both were superseded and left the library in round 5 (git history has them).
+#include "attn_route.h"
 #include "bv_common.h"
 #include "bvhip_internal.h"
 
@@ -142,18 +142,23 @@ int bv_attn3_fwd(const void* qkv, void* o, float* lse, const int* kv_len, int n,
 int bv_attn3_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv,
                  float* dbias, const int* kv_len, int n, int L, int H, void* stream, const bv_ctx* ctx);
 
+// Checks shared by the four entry points below; a, b: the pointers accessed in 16-byte pieces (NULL: none to check)
+static int attn64_check(const char* who, int n, int L, int H, const void* a, const void* b) {
+  BV_REQUIRE(n > 0 && L > 0 && H > 0, "%s: bad shape n=%d L=%d H=%d", who, n, L, H);
+  BV_REQUIRE(!bvattn::attn_route_is_adh(L, DH), "%s: L=%d > 576 not supported", who, L);
+  BV_REQUIRE((uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0, "%s: unaligned pointers", who);
+  return 0;
+}
+
 extern "C" int bv_attn_fwd(const void* qkv, void* o, float* lse, int n, int L, int H, void* stream, const bv_ctx* ctx) {
-  BV_REQUIRE(n > 0 && L > 0 && H > 0, "bv_attn_fwd: bad shape n=%d L=%d H=%d", n, L, H);
-  BV_REQUIRE(L <= 576, "bv_attn_fwd: L=%d > 576 not supported", L);
-  BV_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)o % 16 == 0, "bv_attn_fwd: unaligned pointers");
+  if (const int rc = attn64_check("bv_attn_fwd", n, L, H, qkv, o)) return rc;
   return bv_attn3_fwd(qkv, o, lse, nullptr, n, L, H, stream, ctx);
 }
 
 extern "C" int bv_attn_bwd(const void* qkv, const void* o, const void* d_o, const float* lse,
                            float* delta, void* dqkv, float* dbias_rows, int n, int L, int H, void* stream,
                            const bv_ctx* ctx) {
-  BV_REQUIRE(n > 0 && L > 0 && H > 0, "bv_attn_bwd: bad shape n=%d L=%d H=%d", n, L, H);
-  BV_REQUIRE(L <= 576, "bv_attn_bwd: L=%d > 576 not supported", L);
+  if (const int rc = attn64_check("bv_attn_bwd", n, L, H, nullptr, nullptr)) return rc;
   return bv_attn3_bwd(qkv, o, d_o, lse, delta, dqkv, dbias_rows, nullptr, n, L, H, stream, ctx);
 }
 
@@ -164,16 +169,13 @@ extern "C" int bv_attn_bwd(const void* qkv, const void* o, const void* d_o, cons
 // (NaFlex pads at the end).  kv_len = NULL: no mask.
 extern "C" int bv_attn_fwd_masked(const void* qkv, void* o, float* lse, const int* kv_len, int n, int L, int H,
                                   void* stream, const bv_ctx* ctx) {
-  BV_REQUIRE(n > 0 && L > 0 && H > 0, "bv_attn_fwd_masked: bad shape n=%d L=%d H=%d", n, L, H);
-  BV_REQUIRE(L <= 576, "bv_attn_fwd_masked: L=%d > 576 not supported", L);
-  BV_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)o % 16 == 0, "bv_attn_fwd_masked: unaligned pointers");
+  if (const int rc = attn64_check("bv_attn_fwd_masked", n, L, H, qkv, o)) return rc;
   return bv_attn3_fwd(qkv, o, lse, kv_len, n, L, H, stream, ctx);
 }
 extern "C" int bv_attn_bwd_masked(const void* qkv, const void* d_o, const float* lse, const int* kv_len,
                                   float* delta, void* dqkv, float* dbias_rows, int n, int L, int H, void* stream,
                                   const bv_ctx* ctx) {
-  BV_REQUIRE(n > 0 && L > 0 && H > 0, "bv_attn_bwd_masked: bad shape n=%d L=%d H=%d", n, L, H);
-  BV_REQUIRE(L <= 576, "bv_attn_bwd_masked: L=%d > 576 not supported", L);
+  if (const int rc = attn64_check("bv_attn_bwd_masked", n, L, H, nullptr, nullptr)) return rc;
   return bv_attn3_bwd(qkv, nullptr, d_o, lse, delta, dqkv, dbias_rows, kv_len, n, L, H, stream, ctx);
 }
 

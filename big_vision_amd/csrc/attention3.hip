@@ -33,6 +33,7 @@
 // dP = dO V^T and accumulates dV^T += dO^T P, dK^T += Q^T dS.
 #include <type_traits>
 #include "attn_common.h"
+#include "attn_route.h"   // which instantiation serves a launch, and the A3_FWD_LONG_NW / A3_DQ_LONG_NW workgroup sizes
 #include "bvhip_internal.h"
 // scheduling fences of the forward loops at 3 workgroups per CU (168 VGPRs): one behind every A3_SB_S-th score
 // fragment / every A3_SB_PV-th pair of P V fragments bounds how many LDS operand reads hipcc hoists (0 = none)
@@ -50,12 +51,6 @@
 #ifndef A4_DKV_PIPE
 #define A4_DKV_PIPE 0    // 1: the 32-key-block dK / dV kernel requests the Q / dO rows of the NEXT query fragment before the current
 #endif                   //    fragment's MFMAs / exponentials: bit-identical, +0.5..1 % SLOWER (same file) - not adopted
-#ifndef A3_FWD_LONG_NW
-#define A3_FWD_LONG_NW 8   // waves of the 28-fragment forward's workgroup: 8 (2 per SIMD, K-row prefetch) or 12 (3 per SIMD, plain loops,
-#endif                     // 166 VGPRs): 12 is bit-identical and 2 % faster (433 vs 442 us, r06_attn_long_prefetch_ab.txt) - inside the spread, off
-#ifndef A3_DQ_LONG_NW
-#define A3_DQ_LONG_NW 16   // waves of the UNMASKED 28-fragment one-sweep dQ kernel: 16 (4 per SIMD: its 126 VGPRs fit the 128 line) ships since
-#endif                     // round 6 - bit-identical, backward at L = 441 1424-1430 -> 1384-1400 us (same file); 8 = the former 2 per SIMD
 #ifndef A3_SB_S
 #define A3_SB_S 4
 #endif
@@ -964,20 +959,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_bwd_dkv_kernel(const bf16* _
   }
 }
 
-// A/B switches of a launch, decoded from the caller's BV_OPT_ATTN_CFG (include/bvhip.h)
-struct A3Cfg {
-  bool fwd8;        // bit 8:   forward of the L <= 208 kernels as 8 waves x 2 workgroups
-  bool one_sweep;   // !bit 16: one-sweep dQ kernel (default); bit 16 = always the two-sweep kernel
-  int dkv32;        // bits 32 / 64: 32-key-block dK/dV kernel, 1 = 4 waves x 2 workgroups per CU, 2 = 7 waves x 1
-  bool a5_off;      // bit 128: keep the two-launch backward also where the one-launch kernel (attention5.hip) applies
-  bool a5_bias_dpp; // bit 256: attention5.hip reduces the bias gradients with DPP column sums instead of the identities
-  bool dkv_classic; // bit 1024: the 16-key-fragment dK/dV kernel also for the long sequences (28+ fragments), see launch_bwd3
-};
-A3Cfg a3cfg(const bv_ctx* ctx) {
-  const long c = bv_opt(ctx, BV_OPT_ATTN_CFG);
-  return A3Cfg{(c & 15) == 8, !(c & 16), (c & 64) ? 2 : (c & 32) ? 1 : 0, (c & 128) != 0, (c & 256) != 0, (c & 1024) != 0};
-}
-
 template <typename K>
 void set_lds(K kernel, size_t bytes) {
   if (bytes > 65536)
@@ -985,111 +966,80 @@ void set_lds(K kernel, size_t bytes) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <int KF, int NW, int WPS>
-int launch_fwd3(const void* qkv, void* o, float* lse, const int* kv_len, int n, int L, int H, hipStream_t s) {
-  const size_t sh = (size_t)KF * 4096;
-  if (!kv_len && L > (KF - 1) * 16) {
-    set_lds(attn3_fwd_kernel<KF, NW, WPS, true>, sh);
-    hipLaunchKernelGGL((attn3_fwd_kernel<KF, NW, WPS, true>), dim3(n * H), dim3(NW * 64), sh, s, (const bf16*)qkv,
-                       (bf16*)o, lse, kv_len, L, H, 0.125f);
-  } else {
-    set_lds(attn3_fwd_kernel<KF, NW, WPS, false>, sh);
-    hipLaunchKernelGGL((attn3_fwd_kernel<KF, NW, WPS, false>), dim3(n * H), dim3(NW * 64), sh, s, (const bf16*)qkv,
-                       (bf16*)o, lse, kv_len, L, H, 0.125f);
-  }
+// The launchers instantiate, from the geometry tables of attn_route.h, every kernel attn_route() can name for their KF
+// and launch the one the route names: one workgroup per (sample, head).
+template <int KF, bool FWD8 = false>
+int launch_fwd3(const AttnRoute& r, const void* qkv, void* o, float* lse, const int* kv_len, int n, int L, int H,
+                hipStream_t s) {
+  constexpr AttnGeom G = attn3_fwd_geom(KF, FWD8);
+  auto go = [&](auto kern) __attribute__((always_inline)) {
+    const size_t sh = (size_t)KF * 4096;
+    set_lds(kern, sh);
+    hipLaunchKernelGGL(kern, dim3(n * H), dim3(G.NW * 64), sh, s, (const bf16*)qkv, (bf16*)o, lse, kv_len, L, H, 0.125f);
+  };
+  if (r.tail) go(attn3_fwd_kernel<KF, G.NW, G.WPS, true>);
+  else go(attn3_fwd_kernel<KF, G.NW, G.WPS, false>);
   return bv_check_launch("bv_attn_fwd");
 }
-// NW / WPS: the dQ kernel, NW2 / WPS2: the dK,dV kernel (waves per workgroup / per SIMD)
-template <int KF, int NW, int WPS, int WPS2, int NW2 = NW>
-int launch_bwd3(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv,
-                float* dbias, const int* kv_len, int n, int L, int H, hipStream_t s, const A3Cfg& cfg) {
-  const bool g_a3_one_sweep = cfg.one_sweep;
-  // Long sequences (28+ key fragments: L/16 at 336 px = 441 tokens, 576 at 384 px), unmasked: the 32-key-block dK/dV
-  // kernel with 7 waves is the default since round 6 - bit-identical results, whole backward 1360 -> 1249 us at n = 256,
-  // L = 441, H = 16 and 716 -> 686 us at L = 576 (tools/attn_longseq_cfg_ab.py, profiles/r06_attn_longseq_cfg_ab.txt);
-  // at 13-17 fragments it loses (L = 256: 366 -> 461 us) and stays opt-in
-  const int g_a4_dkv = cfg.dkv32 ? cfg.dkv32 : ((KF >= 28 && !kv_len && !cfg.dkv_classic) ? 2 : 0);
-  const size_t sh1 = (size_t)KF * 4096 + (size_t)NW * 64 * 4;
-  if (o && g_a3_one_sweep) {
-    if (!kv_len && L > (KF - 1) * 16) {
-      constexpr int NWT = (KF == 28 && A3_DQ_LONG_NW == 16) ? 16 : NW, WPST = (KF == 28 && A3_DQ_LONG_NW == 16) ? 4 : WPS;
-      const size_t sh1 = (size_t)KF * 4096 + (size_t)NWT * 64 * 4;
-      set_lds(attn3_bwd_dq1_kernel<KF, NWT, WPST, true>, sh1);
-      hipLaunchKernelGGL((attn3_bwd_dq1_kernel<KF, NWT, WPST, true>), dim3(n * H), dim3(NWT * 64), sh1, s,
-                         (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len,
-                         L, H, 0.125f);
-    } else {
-      set_lds(attn3_bwd_dq1_kernel<KF, NW, WPS, false>, sh1);
-      hipLaunchKernelGGL((attn3_bwd_dq1_kernel<KF, NW, WPS, false>), dim3(n * H), dim3(NW * 64), sh1, s,
-                         (const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len,
-                         L, H, 0.125f);
-    }
-  } else {
-    set_lds(attn3_bwd_dq_kernel<KF, NW, WPS>, sh1);
-    hipLaunchKernelGGL((attn3_bwd_dq_kernel<KF, NW, WPS>), dim3(n * H), dim3(NW * 64), sh1, s, (const bf16*)qkv,
-                       (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
-  }
-  int rc = bv_check_launch("bv_attn_bwd(dq)");
-  if (rc) return rc;
-  // 32-key blocks (A/B: BV_OPT_ATTN_CFG bits 32 = 4 waves x 2 workgroups, 64 = 7 waves x 1); compile-time KF guard: the
-  // 4-fragment sequences (L <= 64) always take the classic kernel, so no attn4 instantiation exists for them
-  if constexpr (KF >= 13) {
-    if (g_a4_dkv) {
-      if (g_a4_dkv == 2) {
-        const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)7 * 128 * 4;
-        set_lds(attn4_bwd_dkv_kernel<KF, 7>, sh);
-        hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 7>), dim3(n * H), dim3(7 * 64), sh, s, (const bf16*)qkv,
-                           (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
-      } else {
-        const size_t sh = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)4 * 128 * 4;
-        set_lds(attn4_bwd_dkv_kernel<KF, 4>, sh);
-        hipLaunchKernelGGL((attn4_bwd_dkv_kernel<KF, 4>), dim3(n * H), dim3(4 * 64), sh, s, (const bf16*)qkv,
-                           (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
-      }
+template <int KF>
+int launch_bwd3(const AttnRoute& r, const void* qkv, const void* o, const void* d_o, const float* lse, float* delta,
+                void* dqkv, float* dbias, const int* kv_len, int n, int L, int H, hipStream_t s) {
+  constexpr AttnGeom G = attn3_bwd_geom(KF), GT = attn3_dq1_tail_geom(KF);
+  // the kernels' arguments differ only behind qkv: the one-sweep dQ kernel also reads O
+  auto go = [&](auto kern, int nw, size_t lds, auto... o_) __attribute__((always_inline)) {
+    const size_t sh = (size_t)KF * 4096 + lds;
+    set_lds(kern, sh);
+    hipLaunchKernelGGL(kern, dim3(n * H), dim3(nw * 64), sh, s, (const bf16*)qkv, o_..., (const bf16*)d_o, lse, delta,
+                       (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
+  };
+  auto dq_lds = [](int nw) { return (size_t)nw * 64 * 4; };
+  auto dkv_lds = [](int nw) { return (size_t)KF * 16 * 8 + (size_t)nw * 128 * 4; };
+  if (r.dq1 && r.tail) go(attn3_bwd_dq1_kernel<KF, GT.NW, GT.WPS, true>, GT.NW, dq_lds(GT.NW), (const bf16*)o);
+  else if (r.dq1) go(attn3_bwd_dq1_kernel<KF, G.NW, G.WPS, false>, G.NW, dq_lds(G.NW), (const bf16*)o);
+  else go(attn3_bwd_dq_kernel<KF, G.NW, G.WPS>, G.NW, dq_lds(G.NW));
+  if (const int rc = bv_check_launch("bv_attn_bwd(dq)")) return rc;
+  if constexpr (attn4_dkv_exists(KF)) {
+    if (r.dkv_kind != DKV_16) {
+      if (r.dkv_kind == DKV_32X7) go(attn4_bwd_dkv_kernel<KF, 7>, 7, dkv_lds(7));
+      else go(attn4_bwd_dkv_kernel<KF, 4>, 4, dkv_lds(4));
       return bv_check_launch("bv_attn_bwd(dkv32)");
     }
   }
-  const size_t sh2 = (size_t)KF * 4096 + (size_t)KF * 16 * 8 + (size_t)NW2 * 128 * 4;
-  set_lds(attn3_bwd_dkv_kernel<KF, NW2, WPS2>, sh2);
-  hipLaunchKernelGGL((attn3_bwd_dkv_kernel<KF, NW2, WPS2>), dim3(n * H), dim3(NW2 * 64), sh2, s, (const bf16*)qkv,
-                     (const bf16*)d_o, lse, delta, (bf16*)dqkv, dbias, kv_len, L, H, 0.125f);
+  go(attn3_bwd_dkv_kernel<KF, G.NW, G.WPS>, G.NW, dkv_lds(G.NW));
   return bv_check_launch("bv_attn_bwd(dkv)");
 }
 
 }  // namespace
 
-// Entry points used by bv_attn_fwd / bv_attn_bwd (attention.hip).  Key fragments = ceil(L/16) for
-// the common sequence lengths (64 text tokens; 196/197 at 224 px; 256/257; 441 at 336 px; 576 at
-// 384 px), the next instantiated size otherwise.
-// attention5.hip: the backward in one launch (unmasked, L <= 64 or 193..208); -100 = shape not covered
+// attention5.hip: the backward in one launch, for the shapes attn_route() gives to ATTN_5
 int bv_attn5_bwd(const void* qkv, const void* d_o, const float* lse, float* delta, void* dqkv, float* dbias, int n,
                  int L, int H, void* stream, bool bias_dpp);
 
+// Entry points used by bv_attn_fwd / bv_attn_bwd (attention.hip): Dh = 64, L <= 576 (never ATTN_ADH).
 int bv_attn3_fwd(const void* qkv, void* o, float* lse, const int* kv_len, int n, int L, int H, void* stream,
                  const bv_ctx* ctx) {
   hipStream_t s = (hipStream_t)stream;
-  const A3Cfg cfg = a3cfg(ctx);
-  if (L <= 64) return launch_fwd3<4, 4, 4>(qkv, o, lse, kv_len, n, L, H, s);
-  // 13 key fragments: 4 waves per workgroup and 3 workgroups per CU (the third one computes while
-  // another stages its K/V: 605-650 us instead of 670-730 at n = 2048); 8 waves x 2 under BV_OPT_ATTN_CFG = 8
-  if (L <= 208 && cfg.fwd8) return launch_fwd3<13, 8, 4>(qkv, o, lse, kv_len, n, L, H, s);
-  if (L <= 208) return launch_fwd3<13, 4, 3>(qkv, o, lse, kv_len, n, L, H, s);
-  if (L <= 272) return launch_fwd3<17, 8, 4>(qkv, o, lse, kv_len, n, L, H, s);
-  if (L <= 448) return launch_fwd3<28, A3_FWD_LONG_NW, A3_FWD_LONG_NW == 12 ? 3 : 2>(qkv, o, lse, kv_len, n, L, H, s);
-  return launch_fwd3<36, 8, 2>(qkv, o, lse, kv_len, n, L, H, s);
+  const AttnRoute r = attn_route(L, DH, kv_len != nullptr, bv_opt(ctx, BV_OPT_ATTN_CFG), true);
+  switch (r.KF) {
+    case 4: return launch_fwd3<4>(r, qkv, o, lse, kv_len, n, L, H, s);
+    case 13: return r.fwd8 ? launch_fwd3<13, true>(r, qkv, o, lse, kv_len, n, L, H, s)
+                           : launch_fwd3<13>(r, qkv, o, lse, kv_len, n, L, H, s);
+    case 17: return launch_fwd3<17>(r, qkv, o, lse, kv_len, n, L, H, s);
+    case 28: return launch_fwd3<28>(r, qkv, o, lse, kv_len, n, L, H, s);
+    default: return launch_fwd3<36>(r, qkv, o, lse, kv_len, n, L, H, s);
+  }
 }
 
 int bv_attn3_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv,
                  float* dbias, const int* kv_len, int n, int L, int H, void* stream, const bv_ctx* ctx) {
   hipStream_t s = (hipStream_t)stream;
-  const A3Cfg cfg = a3cfg(ctx);
-  if (!kv_len && !cfg.a5_off) {
-    const int rc = bv_attn5_bwd(qkv, d_o, lse, delta, dqkv, dbias, n, L, H, stream, cfg.a5_bias_dpp);
-    if (rc != -100) return rc;
+  const AttnRoute r = attn_route(L, DH, kv_len != nullptr, bv_opt(ctx, BV_OPT_ATTN_CFG), o != nullptr);
+  if (r.family == ATTN_5) return bv_attn5_bwd(qkv, d_o, lse, delta, dqkv, dbias, n, L, H, stream, r.bias_dpp);
+  switch (r.KF) {
+    case 4: return launch_bwd3<4>(r, qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s);
+    case 13: return launch_bwd3<13>(r, qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s);
+    case 17: return launch_bwd3<17>(r, qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s);
+    case 28: return launch_bwd3<28>(r, qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s);
+    default: return launch_bwd3<36>(r, qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s);
   }
-  if (L <= 64) return launch_bwd3<4, 4, 4, 4>(qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s, cfg);
-  if (L <= 208) return launch_bwd3<13, 8, 4, 4>(qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s, cfg);
-  if (L <= 272) return launch_bwd3<17, 8, 4, 4>(qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s, cfg);
-  if (L <= 448) return launch_bwd3<28, 8, 2, 2>(qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s, cfg);
-  return launch_bwd3<36, 8, 2, 2>(qkv, o, d_o, lse, delta, dqkv, dbias, kv_len, n, L, H, s, cfg);
 }

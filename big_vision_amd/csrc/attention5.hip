@@ -31,6 +31,7 @@
 // 4 planes x 32 contiguous bytes per lane group of 16, planes 16 dwords apart mod 64 banks: conflict-free both ways.
 #include <type_traits>
 #include "attn_common.h"
+#include "attn_route.h"
 #include "bvhip_internal.h"
 #ifndef A5_UNROLL_1A
 #define A5_UNROLL_1A 16   // fully unrolled (like 1b and phase 2): every LDS address is a base register + an immediate
@@ -733,12 +734,10 @@ template <int KF, int LW>
 int launch_bwd5(const void* qkv, const void* d_o, const float* lse, void* dqkv, float* dbias, int n, int L, int H,
                 hipStream_t s, bool bias_dpp) {
   using C = A5<KF, LW>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
+  // the persistent grid is sized for the device this launch runs on: asked per launch, nothing is kept between calls
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   // workgroups per CU: LDS (160 KiB) and 5 waves per SIMD (<= 96 VGPRs: the KF = 4 instantiations; 13 + 3 waves fill a CU)
   int per_cu = (160 * 1024) / C::LDS;
   if (per_cu > 20 / (KF + LW)) per_cu = 20 / (KF + LW);
@@ -760,13 +759,13 @@ int launch_bwd5(const void* qkv, const void* d_o, const float* lse, void* dqkv, 
 
 }  // namespace
 
-// Entry used by bv_attn3_bwd (attention3.hip) for unmasked sequences of at most 208 tokens; returns -100 when the
-// shape is not covered (the caller keeps the two-launch path).
+// Entry used by bv_attn3_bwd (attention3.hip) for the unmasked sequences attn_route() gives to ATTN_5.
 int bv_attn5_bwd(const void* qkv, const void* d_o, const float* lse, float* delta, void* dqkv, float* dbias, int n,
                  int L, int H, void* stream, bool bias_dpp) {
   hipStream_t s = (hipStream_t)stream;
   (void)delta;   // scratch of the two-launch path; the exact delta never leaves the LDS here
-  if (L <= 64) return launch_bwd5<4, 1>(qkv, d_o, lse, dqkv, dbias, n, L, H, s, bias_dpp);
-  if (L > 192 && L <= 208) return launch_bwd5<13, 3>(qkv, d_o, lse, dqkv, dbias, n, L, H, s, bias_dpp);
-  return -100;
+  BV_REQUIRE(attn5_lw(L) != 0, "bv_attn_bwd(one launch): L=%d is not a shape of the one-launch backward", L);
+  // the loader waves of a bucket: those of its longest sequence
+  if (attn3_kf(L) == 4) return launch_bwd5<4, attn5_lw(64)>(qkv, d_o, lse, dqkv, dbias, n, L, H, s, bias_dpp);
+  return launch_bwd5<13, attn5_lw(208)>(qkv, d_o, lse, dqkv, dbias, n, L, H, s, bias_dpp);
 }

@@ -259,10 +259,19 @@ def _head_dim(numel, rows, parts, H, what):
   return Dh
 
 
+def _self_attn_entry(L, Dh, masked):
+  """Suffix of the bv_attn_fwd / bv_attn_bwd entry point of a shape: "_dh" where csrc/attn_route.h attn_route_is_adh()."""
+  return "_dh" if Dh != 64 or L > 576 else "_masked" if masked else ""
+
+
+def _map_attn_entry(L, Dh, masked):
+  """The same for bv_map_attn_fwd / _bwd (MAP head): the Dh = 64 kernels keep a row of up to 2048 probabilities in LDS."""
+  return "_dh" if Dh != 64 or L > 2048 else "_masked" if masked else ""
+
+
 def attn_fwd(qkv, n, L, H, kv_len=None):
-  """qkv [n*L, 3*H*Dh] (Dh inferred; 64 takes the LDS-resident kernels, other multiples of 8 up to 128
-  and sequences longer than 576 the general ones).  kv_len (int32 [n], optional): valid keys per sample
-  (key-padding mask of the NaFlex tower)."""
+  """qkv [n*L, 3*H*Dh] (Dh inferred; which kernel serves the shape is decided by csrc/attn_route.h).  kv_len (int32
+  [n], optional): valid keys per sample (key-padding mask of the NaFlex tower)."""
   _chk(qkv, BF16, "attn.qkv")
   assert qkv.is_contiguous()
   Dh = _head_dim(qkv.numel(), n * L, 3, H, "attn_fwd")
@@ -271,9 +280,10 @@ def attn_fwd(qkv, n, L, H, kv_len=None):
   if kv_len is not None:
     _chk(kv_len, torch.int32, "attn.kv_len")
     assert kv_len.is_contiguous() and kv_len.numel() == n
-  if Dh != 64 or L > 576:
+  entry = _self_attn_entry(L, Dh, kv_len is not None)
+  if entry == "_dh":
     _lib.call("bv_attn_fwd_dh", _p(qkv), _p(o), _p(lse), _p(kv_len), n, L, H, Dh, _stream())
-  elif kv_len is not None:
+  elif entry == "_masked":
     _lib.call("bv_attn_fwd_masked", _p(qkv), _p(o), _p(lse), _p(kv_len), n, L, H, _stream(), ctx().ptr)
   else:
     _lib.call("bv_attn_fwd", _p(qkv), _p(o), _p(lse), n, L, H, _stream(), ctx().ptr)
@@ -283,8 +293,8 @@ def attn_fwd(qkv, n, L, H, kv_len=None):
 def attn_bwd(qkv, o, d_o, lse, n, L, H, dqkv=None, dbias=None, kv_len=None, delta=None):
   """dbias (fp32, 3*H*Dh elements): += column sums of dqkv (the q/k/v bias gradients).
   delta (fp32 [n, H, L], optional): the caller's buffer for the kernels' rowsum(P o dP) scratch, so that tests can
-  read it back; the one-launch backward (unmasked Dh = 64, L <= 64 or 193..208) keeps it in LDS and leaves the
-  buffer untouched."""
+  read it back; the one-launch backward (family ATTN_5 of csrc/attn_route.h, which decides the kernels) keeps it in
+  LDS and leaves the buffer untouched."""
   _chk(qkv, BF16, "attn.qkv"); _chk(o, BF16, "attn.o"); _chk(d_o, BF16, "attn.do")
   assert d_o.is_contiguous() and o.is_contiguous()
   Dh = _head_dim(qkv.numel(), n * L, 3, H, "attn_bwd")
@@ -301,10 +311,11 @@ def attn_bwd(qkv, o, d_o, lse, n, L, H, dqkv=None, dbias=None, kv_len=None, delt
   rows = torch.empty((n, 3 * H * Dh), device=qkv.device, dtype=F32) if dbias is not None else None
   if kv_len is not None:
     _chk(kv_len, torch.int32, "attn.kv_len")
-  if Dh != 64 or L > 576:
+  entry = _self_attn_entry(L, Dh, kv_len is not None)
+  if entry == "_dh":
     _lib.call("bv_attn_bwd_dh", _p(qkv), _p(d_o), _p(lse), _p(kv_len), _p(delta), _p(dqkv), _p(rows),
               n, L, H, Dh, _stream())
-  elif kv_len is not None:
+  elif entry == "_masked":
     _lib.call("bv_attn_bwd_masked", _p(qkv), _p(d_o), _p(lse), _p(kv_len), _p(delta), _p(dqkv), _p(rows),
               n, L, H, _stream(), ctx().ptr)
   else:
@@ -324,9 +335,10 @@ def map_attn_fwd(q, kv, n, L, H, kv_len=None):
   p = torch.empty((n, H, L), device=q.device, dtype=F32)
   if kv_len is not None:
     _chk(kv_len, torch.int32, "map_attn.kv_len")
-  if Dh != 64 or L > 2048:
+  entry = _map_attn_entry(L, Dh, kv_len is not None)
+  if entry == "_dh":
     _lib.call("bv_map_attn_fwd_dh", _p(q), _p(kv), _p(o), _p(p), _p(kv_len), n, L, H, Dh, _stream())
-  elif kv_len is not None:
+  elif entry == "_masked":
     _lib.call("bv_map_attn_fwd_masked", _p(q), _p(kv), _p(o), _p(p), _p(kv_len), n, L, H, _stream())
   else:
     _lib.call("bv_map_attn_fwd", _p(q), _p(kv), _p(o), _p(p), n, L, H, _stream())
@@ -339,7 +351,7 @@ def map_attn_bwd(q, kv, p, d_o, n, L, H):
   Dh = _head_dim(q.numel(), n, 1, H, "map_attn_bwd")
   dq = torch.empty_like(q)
   dkv = torch.empty_like(kv)
-  if Dh != 64 or L > 2048:
+  if _map_attn_entry(L, Dh, False) == "_dh":   # the backward works from the saved probabilities: no mask
     _lib.call("bv_map_attn_bwd_dh", _p(q), _p(kv), _p(p), _p(d_o), _p(dq), _p(dkv), n, L, H, Dh, _stream())
   else:
     _lib.call("bv_map_attn_bwd", _p(q), _p(kv), _p(p), _p(d_o), _p(dq), _p(dkv), n, L, H, _stream())

@@ -15,8 +15,8 @@
  *     returns immediately: 0 = ok, <0 = error (BV_ERR_*); the message is
  *     available from bv_last_error().  No call synchronises.
  *   - thread-safe per stream.  The library keeps NO process-global state besides the (thread-local)
- *     last-error string (what else is static is immutable after its first use: the compute-unit count of
- *     the device, the kernel attributes the HIP runtime caches, the RCCL entry points bv_comm_* binds): every option
+ *     last-error string (what else is static is immutable after its first use: the kernel attributes
+ *     the HIP runtime caches, the RCCL entry points bv_comm_* binds; device properties are asked per launch): every option
  *     that selects a kernel variant, the split-K workspace and the launch counters live in an opaque
  *     `bv_ctx` the caller creates and passes to the entry points that consult it (GEMM, attention,
  *     fp32 GEMM).  ctx = NULL means "all defaults, no workspace".  Two callers in one process that

@@ -427,7 +427,9 @@ def attn_fwd_bounds(qkv, n, L, H, Dh, lens=None):
 
 
 # --------------------------------------------------- attention backward ----
-# What the kernels document (headers and comments of attention3.hip, attention5.hip, attention_dh.hip), per path:
+# What the kernels document (headers and comments of attention3.hip, attention5.hip, attention_dh.hip), per path.
+# Which shape takes which path is decided by big_vision_amd/csrc/attn_route.h; attn_bwd_path below restates it for the
+# error models and is held to that header for every shape by tests/test_attn_route_cpu.py.
 #   every path   S and dP fp32-accumulated over Dh; P = exp2(S c - lse log2 e) from the STORED fp32 lse (so P carries
 #                the forward's lse error); dS = P o (dP - delta) in fp32; dV takes bf16(P), dQ / dK take bf16(dS) as
 #                MFMA operands, accumulated over L in fp32; 1 / sqrt(Dh) (0.125 exactly at Dh = 64, the fp32
@@ -438,7 +440,7 @@ def attn_fwd_bounds(qkv, n, L, H, Dh, lens=None):
 #                dS~ = P o (dP - delta~), eps = rowsum(dS~), dQ = sum bf16(dS~) K - eps sum bf16(P) K, delta = delta~
 #                + eps is stored for the dK / dV launch.  In exact arithmetic that is P o (dP - delta) with delta =
 #                rowsum(P o dP) + delta~ (1 - rowsum P): the terms below marked "dq1".
-#   attn5        (unmasked Dh = 64, L <= 64 or 193..208) one launch: delta as attn3 dq but kept in LDS (never
+#   attn5        (the route's ATTN_5 family) one launch: delta as attn3 dq but kept in LDS (never
 #                stored: the delta buffer is NOT filled on this path); phase 1b forms dS from the bf16 P of the LDS
 #                image, so dS carries one more 2^-8 rounding: the terms marked "attn5".
 #   bias rows    every path sums the fp32 accumulators (after the scale, BEFORE the bf16 rounding) over a (sample,
@@ -465,7 +467,7 @@ NO_LEGACY = (0.0, float("inf"))   # for outputs that no earlier assertion covere
 
 
 def attn_bwd_path(L, Dh, masked, one_launch=True):
-  """The kernel family ops.attn_bwd dispatches to (attention.hip / attention3.hip bv_attn3_bwd)."""
+  """The kernel family ops.attn_bwd dispatches to: the mirror of csrc/attn_route.h (see the comment block above)."""
   if Dh != 64 or L > 576:
     return "adh"
   if masked:

@@ -4,12 +4,10 @@ plain fp64 statement of the op on the same bf16-rounded inputs.
 
 Every row id names the instantiation and the host branch that selects it, so the tables below read against the
 dispatchers without running anything:
-  attention3.hip  bv_attn3_fwd / bv_attn3_bwd: `L <= 64 / 208 / 272 / 448 / else` -> KF = 4 / 13 / 17 / 28 / 36;
-                  launch_fwd3 / launch_bwd3: TAIL = unmasked and L > (KF - 1) * 16; the masked backward has no `o`
-                  (two-sweep dQ kernel); dK/dV: attn4 (32-key blocks) for KF >= 28 unmasked, attn3 otherwise;
-                  a3cfg: BV_OPT_ATTN_CFG bits 8 / 16 / 32 / 64 / 128 / 256 / 1024
-  attention5.hip  bv_attn5_bwd: unmasked L <= 64 or 193..208 (BM: 0 no dbias, 1 DPP, 2 L % 16, 3 identities)
-  attention_dh.hip BV_ADH_DISPATCH: (Dh + 15) / 16 = 1..8; Dh = 64 with L > 576
+  attention3.hip, attention5.hip: csrc/attn_route.h attn_route() names the instantiation for every (L, Dh, masked,
+                  BV_OPT_ATTN_CFG); tests/test_attn_route_cpu.py holds the ATTN64 / ATTN_CFG tables below to it.
+                  attention5.hip launch_bwd5 adds BM: 0 no dbias, 1 DPP, 2 L % 16, 3 identities
+  attention_dh.hip BV_ADH_DISPATCH: (Dh + 15) / 16 = 1..8; entered where attn_route_is_adh() says so
   layernorm.hip   bv_layernorm_fwd / _bwd_y: NV = 3 (D <= 768) / 4 (<= 1024) / 8, NT = ln_nt_for (rows * D * 4 > 192 MiB);
                   bv_layernorm_bwd_bf16x: bf16 dy -> ln_bwd_bfx2_kernel<nv4 = 3/4/5/8, FULL = D == NV * 256, RES>,
                   fp32 dy -> ln_bwd_bfx_kernel<true, D <= 1024 ? 2 : 4>; bv_layernorm_fwd_bf16x NV = 3/4/5/8
@@ -56,7 +54,7 @@ def _attn_check(dev, n, L, H, Dh, masked, cfg=None, seed=0):
   # masks: full, a quarter (another bucket's length) and one short of L (cuts the tail fragment)
   lens = [L, max(1, L // 4), max(1, L - 1)][:n] if masked else [L] * n
   kv_len = torch.tensor(lens, device=dev, dtype=torch.int32) if masked else None
-  # the kernel family the launch dispatches to under these A/B bits (attention3.hip bv_attn3_bwd / launch_bwd3)
+  # the kernel family the launch dispatches to under these A/B bits (csrc/attn_route.h)
   c = cfg or 0
   path = B.attn_bwd_path(L, Dh, masked, one_launch=not (c & 128))
   if "dq1" in path and (c & 16):
@@ -134,7 +132,7 @@ ATTN_CFG = [
 def test_attention_cfg_bit(dev, L, masked, bit):
   """Each A/B variant vs fp64.  Where the sources state bit-identical results, also bit-compared with the default
   launch: the DPP bias reduction (bit 256) leaves dqkv unchanged (test_kernels_gpu.py one-launch test), and the
-  classic dK/dV kernel of the long sequences (bit 1024) equals the 32-key-block default (attention3.hip launch_bwd3)."""
+  classic dK/dV kernel of the long sequences (bit 1024) equals the 32-key-block default (csrc/attn_route.h)."""
   n = 3 if masked else 2
   o, lse, dqkv, _ = _attn_check(dev, n, L, 2, 64, masked, cfg=bit, seed=1)
   if bit in (256, 1024):

@@ -49,7 +49,7 @@ def test_ledger_entries_are_covered_or_waived_with_a_reason(ledger):
 
 def test_dead_instantiations_stay_out():
   """The instantiations no dispatch row can reach were removed: attn4_bwd_dkv_kernel<4, *> (launch_bwd3's 32-key-block
-  branch is compile-time KF >= 13) and ln_bwd_bfx_kernel<false, *> (a bf16 dy takes the two-row kernel)."""
+  branch is compile-time attn4_dkv_exists(KF): KF >= 13) and ln_bwd_bfx_kernel<false, *> (a bf16 dy takes the two-row kernel)."""
   with open(KI.LEDGER) as f:
     names = json.load(f)["kernels"]
   assert not [n for n in names if n.startswith("_ZN12_GLOBAL__N_120attn4_bwd_dkv_kernelILi4E")]

@@ -8,7 +8,7 @@
 #include "probe_ctx.h"
 // (attention3.hip hands the unmasked backward to attention5.hip; the forward probe links without it)
 int g_a5_bias_dpp = 0;
-int bv_attn5_bwd(const void*, const void*, const float*, float*, void*, float*, int, int, int, void*, bool) { return -100; }
+int bv_attn5_bwd(const void*, const void*, const float*, float*, void*, float*, int, int, int, void*, bool) { return -1; }
 
 __global__ void fill(unsigned short* p, size_t n, unsigned seed) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {

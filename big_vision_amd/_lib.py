@@ -1,4 +1,4 @@
-"""ctypes binding of libbvhip.so (the C ABI declared in include/bvhip.h).
+"""ctypes binding of libbvhip.so (the C ABI declared in include/bvhip.h) and of libbvdistill.so (include/bvdistill.h).
 
 The product path has NO fallback: if the shared library is missing or a call
 fails, a RuntimeError is raised.  Build it with `python big_vision_amd/build.py`
@@ -16,6 +16,7 @@ from ctypes import c_int, c_long, c_float, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbvhip.so")
+LIB_DISTILL_PATH = os.path.join(_HERE, "libbvdistill.so")
 
 P = c_void_p
 
@@ -108,13 +109,49 @@ OPTS = {"fast_path": 0, "gemm_nt": 1, "gemm_skew_mode": 2, "gemm_skew_pct": 3, "
         "gemm_group_n": 6, "gemm_reserve_cus": 7, "attn_cfg": 8, "sgemm_mfma": 9,
         "gemm256_calls": 100, "gemm256_multi": 101, "gemm256_fused": 102}
 
+# libbvdistill.so (include/bvdistill.h): name -> argtypes, every one returns an int status
+PROTOTYPES_DISTILL = {
+    "bv_distill_version": [],
+    "bv_distill_dist": [c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P],
+    "bv_distill_entropy": [P, P, P, c_int, c_int, c_int, P],
+    "bv_distill_softmax_acc": [P, P, c_float, c_int, c_int, c_int, P],
+}
+# BVD_KIND_* of include/bvdistill.h, by the names of evaluators/proj/distill/distance.py
+DISTILL_KINDS = {"l2": 0, "euclidean": 1, "kl": 2, "hard": 3, "logsoftmax_euclidean": 4, "agree": 5}
+
 EPI_NONE, EPI_RESIDUAL, EPI_POS, EPI_GELU, EPI_GELU_BWD, EPI_ATOMIC, EPI_GELU_BWD_EMIT, EPI_GELU_GD, EPI_MUL, EPI_GELU_G = range(10)
 
 _lib = None
+_lib_distill = None
+
+
+def _load_distill():
+  global _lib_distill
+  if not os.path.exists(LIB_DISTILL_PATH):
+    raise RuntimeError(
+        f"{LIB_DISTILL_PATH} is missing: the HIP extension is not built. Run "
+        "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
+  lib = ctypes.CDLL(LIB_DISTILL_PATH)
+  lib.bv_distill_last_error.restype = ctypes.c_char_p
+  lib.bv_distill_last_error.argtypes = []
+  for name, argtypes in PROTOTYPES_DISTILL.items():
+    fn = getattr(lib, name)  # AttributeError if the ABI drifted
+    fn.restype = c_int
+    fn.argtypes = argtypes
+  if lib.bv_distill_version() != 1:
+    raise RuntimeError("libbvdistill.so ABI version mismatch")
+  _lib_distill = lib
+  return lib
+
+
+def load_distill():
+  """libbvdistill.so (bound by load(), together with libbvhip.so)."""
+  load()
+  return _lib_distill
 
 
 def load():
-  """Loads libbvhip.so (once).  Raises if it is not built — no fallback."""
+  """Loads libbvhip.so and libbvdistill.so (once).  Raises if they are not built — no fallback."""
   global _lib
   if _lib is not None:
     return _lib
@@ -122,6 +159,7 @@ def load():
     raise RuntimeError(
         f"{LIB_PATH} is missing: the HIP extension is not built. Run "
         "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
+  _load_distill()
   lib = ctypes.CDLL(LIB_PATH)
   lib.bv_last_error.restype = ctypes.c_char_p
   lib.bv_last_error.argtypes = []
@@ -142,6 +180,8 @@ observer = None
 
 def call(name, *args):
   lib = load()
+  if name in PROTOTYPES_DISTILL:    # routed to the library whose table holds the name
+    return _call_distill(name, args)
   obs = observer
   tok = obs.begin(name, args) if obs is not None else None
   rc = getattr(lib, name)(*args)
@@ -151,3 +191,14 @@ def call(name, *args):
     return rc
   if rc != 0:
     raise RuntimeError(f"{name} failed (rc={rc}): {lib.bv_last_error().decode()}")
+
+
+def _call_distill(name, args):
+  lib = _lib_distill
+  obs = observer
+  tok = obs.begin(name, args) if obs is not None else None
+  rc = getattr(lib, name)(*args)
+  if tok is not None:
+    obs.end(tok)
+  if rc != 0:
+    raise RuntimeError(f"{name} failed (rc={rc}): {lib.bv_distill_last_error().decode()}")

@@ -1,4 +1,4 @@
-"""Build libbvhip.so (hand-written HIP kernels for gfx950) in-tree with hipcc.
+"""Build libbvhip.so and libbvdistill.so (hand-written HIP kernels for gfx950) in-tree with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the CPU-only
 build container; the resulting big_vision_amd/libbvhip.so travels to the GPU box
@@ -17,57 +17,71 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbvhip.so")
+LIB_DISTILL = os.path.join(HERE, "libbvdistill.so")   # the distillation losses: a library of its own (include/bvdistill.h)
 SOURCES = ["c_api.cpp", "comm.cpp", "gemm_bf16.hip", "gemm256.hip", "attention.hip", "attention3.hip", "attention5.hip", "attention_dh.hip", "layernorm.hip",
            "elementwise.hip", "loss_optim.hip", "adafactor.hip", "dropout.hip"]
+DISTILL_SOURCES = ["distill.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
          "-DNDEBUG"]
+MAX_JOBS = 16   # compiler processes in flight at once
+INCLUDE = os.path.join(HERE, "..", "include")
+LIBS = [(LIB, SOURCES), (LIB_DISTILL, DISTILL_SOURCES)]
+
+
+def _headers():
+  return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
+      os.path.join(INCLUDE, "bvhip.h"), os.path.join(INCLUDE, "bvdistill.h")]
 
 
 def _stale():
-  if not os.path.exists(LIB):
-    return True
-  t = os.path.getmtime(LIB)
-  deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-  deps.append(os.path.join(HERE, "..", "include", "bvhip.h"))
-  return any(os.path.getmtime(d) > t for d in deps)
+  deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _headers()
+  newest = max(os.path.getmtime(d) for d in deps)
+  return any(not os.path.exists(lib) or os.path.getmtime(lib) < newest for lib, _ in LIBS)
 
 
 def build(force=False, verbose=True):
+  """Compiles what is stale and links both libraries; returns the path of libbvhip.so."""
   hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
   if not force and not _stale():
     return LIB
   if not os.path.exists(hipcc):
-    raise RuntimeError("hipcc not found: cannot build libbvhip.so")
+    raise RuntimeError("hipcc not found: cannot build libbvhip.so / libbvdistill.so")
   objdir = os.path.join(HERE, "build")
   os.makedirs(objdir, exist_ok=True)
-  objs = []
-  procs = []
-  headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-  headers.append(os.path.join(HERE, "..", "include", "bvhip.h"))
-  hdr_t = max(os.path.getmtime(h) for h in headers)
-  for src in SOURCES:
+  hdr_t = max(os.path.getmtime(h) for h in _headers())
+  todo = []
+  for src in SOURCES + DISTILL_SOURCES:
     obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
-    objs.append(obj)
     # per-object staleness: only the sources that changed (or everything, after a header edit)
     if (not force and os.path.exists(obj) and
         os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(os.path.join(CSRC, src)))):
       continue
-    cmd = [hipcc, *FLAGS, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
-    if verbose:
-      print(" ".join(cmd), flush=True)
-    procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-  for src, p in procs:
+    todo.append((src, [hipcc, *FLAGS, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]))
+  running = []
+
+  def reap(src, p):
     out, _ = p.communicate()
     if p.returncode != 0:
       sys.stderr.write(out.decode())
       raise RuntimeError(f"hipcc failed on {src}")
-  cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB]
-  if verbose:
-    print(" ".join(cmd), flush=True)
-  subprocess.check_call(cmd)
+
+  for src, cmd in todo:
+    if len(running) >= MAX_JOBS:
+      reap(*running.pop(0))
+    if verbose:
+      print(" ".join(cmd), flush=True)
+    running.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+  for src, p in running:
+    reap(src, p)
+  for lib, sources in LIBS:
+    objs = [os.path.join(objdir, os.path.splitext(src)[0] + ".o") for src in sources]
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib]
+    if verbose:
+      print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
   return LIB
 
 
 if __name__ == "__main__":
   build(force="--force" in sys.argv)
-  print("built", LIB)
+  print("built", LIB, LIB_DISTILL)

@@ -692,3 +692,54 @@ def adafactor_step_(params, grads, momentum, shadow, leaves, nleaves, max_rows, 
             int(max_cols), int(max_b), int(max_total), _p(state), _p(gsq), float(clip_norm or 0.0), float(decay),
             float(eps), float(mom), ctypes.cast(arr, ctypes.c_void_p), len(sched), _p(stats),
             float(block_rms_clip or 0.0), _p(block_usq), _stream())
+
+
+# ---- libbvdistill.so (include/bvdistill.h): the distillation distances, entropy and the teacher-ensemble softmax
+def _logits2d(t, name):
+  _chk(t, F32, name)
+  assert t.dim() == 2 and t.is_contiguous(), f"{name}: expected contiguous fp32 [n, C]"
+  return t.shape
+
+
+def distill_dist(kind, student, teacher, *, loss_sum=None, per_row=False, dstudent=None, want_grad=False, n_global=None,
+                 t=1.0, ls=0.0, eps=1e-12, k=1):
+  """One launch of bv_distill_dist for a (student, teacher) pair of fp32 [n, C] logits; kind: a name of
+  evaluators/proj/distill/distance.py.  loss_sum (f64[1]) += mean over n_global; per_row=True returns the unreduced
+  distances; want_grad=True returns d(mean)/d student in a new tensor, dstudent=<tensor> ADDS it to that tensor
+  (several teachers).  Returns (per_row or None, dstudent or None)."""
+  if kind not in _lib.DISTILL_KINDS:
+    raise AssertionError(f"Unknown kind of distance {kind}.")
+  n, C = _logits2d(student, "distill.student")
+  assert _logits2d(teacher, "distill.teacher") == (n, C), "student and teacher logits differ in shape"
+  assert loss_sum is None or loss_sum.dtype == torch.float64
+  rows = torch.empty((n,), device=student.device, dtype=F32) if per_row else None
+  accumulate = dstudent is not None
+  if accumulate:
+    assert _logits2d(dstudent, "distill.dstudent") == (n, C)
+  elif want_grad:
+    dstudent = torch.empty_like(student)
+  _lib.call("bv_distill_dist", _lib.DISTILL_KINDS[kind], _p(student), _p(teacher), _p(rows), _p(loss_sum), _p(dstudent),
+            int(accumulate), n, C, int(n_global or n), float(t), float(ls), float(eps), int(k), _stream())
+  return rows, dstudent
+
+
+def distill_entropy(logits, *, sum=None, per_row=False, n_global=None):
+  """Entropy of softmax(logits) per row (bv_distill_entropy): sum (f64[1]) += mean over n_global; per_row=True
+  returns the fp32 [n] entropies."""
+  n, C = _logits2d(logits, "entropy.logits")
+  assert sum is None or sum.dtype == torch.float64
+  rows = torch.empty((n,), device=logits.device, dtype=F32) if per_row else None
+  _lib.call("bv_distill_entropy", _p(logits), _p(rows), _p(sum), n, C, int(n_global or n), _stream())
+  return rows
+
+
+def distill_softmax_acc(logits, weight=1.0, probs=None):
+  """probs (+)= weight * softmax(logits) (bv_distill_softmax_acc): a new tensor without `probs`, added to it with."""
+  n, C = _logits2d(logits, "softmax_acc.logits")
+  accumulate = probs is not None
+  if accumulate:
+    assert _logits2d(probs, "softmax_acc.probs") == (n, C)
+  else:
+    probs = torch.empty_like(logits)
+  _lib.call("bv_distill_softmax_acc", _p(logits), _p(probs), float(weight), int(accumulate), n, C, _stream())
+  return probs

@@ -88,18 +88,22 @@ def _load_model_init(model, config, store):
   """train.py:353-359: `model_mod.load(params, config.model_init, config.model, **config.model_load)` into the store.
   Runs before bv_optax.make: the fsdp placement shards the fp32 master there, and a load after it would leave the
   shadow and master views of the earlier layout behind."""
+  load_init(model, store, config.model_init, config.get("model"), config.get("model_load", {}), key="model_init")
+
+
+def load_init(model, store, init, model_cfg, load_kw, key):
+  """`model_mod.load(params, init, model_cfg, **load_kw)` into `store`; `key` names the config field in the errors."""
   model_mod = importlib.import_module(type(model).__module__)
   if not hasattr(model_mod, "load"):
-    raise NotImplementedError(f"config.model_init: {model_mod.__name__} has no load()")
-  init = config.model_init
+    raise NotImplementedError(f"config.{key}: {model_mod.__name__} has no load()")
   path = getattr(model_mod, "VANITY_NAMES", {}).get(init, init) if isinstance(init, str) else init
   if isinstance(path, str) and "://" in path:
-    raise FileNotFoundError(f"config.model_init={init!r} resolves to {path!r}: remote checkpoints cannot be opened "
+    raise FileNotFoundError(f"config.{key}={init!r} resolves to {path!r}: remote checkpoints cannot be opened "
                             "here; download it and pass the local .npz path")
   if isinstance(path, str) and not any(os.path.isfile(p) for p in (path, path.rsplit(":", 1)[0])):
-    raise FileNotFoundError(f"config.model_init={init!r}: no such checkpoint file (remote vanity names are not "
+    raise FileNotFoundError(f"config.{key}={init!r}: no such checkpoint file (remote vanity names are not "
                             "fetched; pass the local .npz path)")
-  params = model_mod.load(store.tree(), init, config.get("model"), **config.get("model_load", {}))
+  params = model_mod.load(store.tree(), init, model_cfg, **load_kw)
   store.load_tree(params)
 
 

@@ -1,4 +1,5 @@
-"""ctypes binding of libbvhip.so (the C ABI declared in include/bvhip.h) and of libbvdistill.so (include/bvdistill.h).
+"""ctypes binding of libbvhip.so (the C ABI declared in include/bvhip.h), of libbvdistill.so (include/bvdistill.h) and
+of libbveval.so (include/bveval.h).
 
 The product path has NO fallback: if the shared library is missing or a call
 fails, a RuntimeError is raised.  Build it with `python big_vision_amd/build.py`
@@ -17,6 +18,7 @@ from ctypes import c_int, c_long, c_float, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbvhip.so")
 LIB_DISTILL_PATH = os.path.join(_HERE, "libbvdistill.so")
+LIB_EVAL_PATH = os.path.join(_HERE, "libbveval.so")
 
 P = c_void_p
 
@@ -119,10 +121,19 @@ PROTOTYPES_DISTILL = {
 # BVD_KIND_* of include/bvdistill.h, by the names of evaluators/proj/distill/distance.py
 DISTILL_KINDS = {"l2": 0, "euclidean": 1, "kl": 2, "hard": 3, "logsoftmax_euclidean": 4, "agree": 5}
 
+# libbveval.so (include/bveval.h): name -> argtypes, every one returns an int status
+PROTOTYPES_EVAL = {
+    "bv_eval_version": [],
+    "bv_eval_classify": [c_int, P, P, P, P, P, P, c_int, c_int, P],
+}
+# BVE_LOSS_* of include/bveval.h, by the `loss_name` of evaluators/classification.py
+EVAL_LOSSES = {"softmax_xent": 0, "sigmoid_xent": 1}
+
 EPI_NONE, EPI_RESIDUAL, EPI_POS, EPI_GELU, EPI_GELU_BWD, EPI_ATOMIC, EPI_GELU_BWD_EMIT, EPI_GELU_GD, EPI_MUL, EPI_GELU_G = range(10)
 
 _lib = None
 _lib_distill = None
+_lib_eval = None
 
 
 def _load_distill():
@@ -150,8 +161,33 @@ def load_distill():
   return _lib_distill
 
 
+def _load_eval():
+  global _lib_eval
+  if not os.path.exists(LIB_EVAL_PATH):
+    raise RuntimeError(
+        f"{LIB_EVAL_PATH} is missing: the HIP extension is not built. Run "
+        "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
+  lib = ctypes.CDLL(LIB_EVAL_PATH)
+  lib.bv_eval_last_error.restype = ctypes.c_char_p
+  lib.bv_eval_last_error.argtypes = []
+  for name, argtypes in PROTOTYPES_EVAL.items():
+    fn = getattr(lib, name)  # AttributeError if the ABI drifted
+    fn.restype = c_int
+    fn.argtypes = argtypes
+  if lib.bv_eval_version() != 1:
+    raise RuntimeError("libbveval.so ABI version mismatch")
+  _lib_eval = lib
+  return lib
+
+
+def load_eval():
+  """libbveval.so (bound by load(), together with the other two libraries)."""
+  load()
+  return _lib_eval
+
+
 def load():
-  """Loads libbvhip.so and libbvdistill.so (once).  Raises if they are not built — no fallback."""
+  """Loads libbvhip.so, libbvdistill.so and libbveval.so (once).  Raises if they are not built — no fallback."""
   global _lib
   if _lib is not None:
     return _lib
@@ -160,6 +196,7 @@ def load():
         f"{LIB_PATH} is missing: the HIP extension is not built. Run "
         "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
   _load_distill()
+  _load_eval()
   lib = ctypes.CDLL(LIB_PATH)
   lib.bv_last_error.restype = ctypes.c_char_p
   lib.bv_last_error.argtypes = []
@@ -181,7 +218,9 @@ observer = None
 def call(name, *args):
   lib = load()
   if name in PROTOTYPES_DISTILL:    # routed to the library whose table holds the name
-    return _call_distill(name, args)
+    return _call_in(_lib_distill, _lib_distill.bv_distill_last_error, name, args)
+  if name in PROTOTYPES_EVAL:
+    return _call_in(_lib_eval, _lib_eval.bv_eval_last_error, name, args)
   obs = observer
   tok = obs.begin(name, args) if obs is not None else None
   rc = getattr(lib, name)(*args)
@@ -193,12 +232,12 @@ def call(name, *args):
     raise RuntimeError(f"{name} failed (rc={rc}): {lib.bv_last_error().decode()}")
 
 
-def _call_distill(name, args):
-  lib = _lib_distill
+def _call_in(lib, last_error, name, args):
+  """One call into a library whose every entry point returns an int status; `last_error` is that library's own."""
   obs = observer
   tok = obs.begin(name, args) if obs is not None else None
   rc = getattr(lib, name)(*args)
   if tok is not None:
     obs.end(tok)
   if rc != 0:
-    raise RuntimeError(f"{name} failed (rc={rc}): {lib.bv_distill_last_error().decode()}")
+    raise RuntimeError(f"{name} failed (rc={rc}): {last_error().decode()}")

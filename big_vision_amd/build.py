@@ -1,4 +1,4 @@
-"""Build libbvhip.so and libbvdistill.so (hand-written HIP kernels for gfx950) in-tree with hipcc.
+"""Build libbvhip.so, libbvdistill.so and libbveval.so (hand-written HIP kernels for gfx950) in-tree with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the CPU-only
 build container; the resulting big_vision_amd/libbvhip.so travels to the GPU box
@@ -21,16 +21,18 @@ LIB_DISTILL = os.path.join(HERE, "libbvdistill.so")   # the distillation losses:
 SOURCES = ["c_api.cpp", "comm.cpp", "gemm_bf16.hip", "gemm256.hip", "attention.hip", "attention3.hip", "attention5.hip", "attention_dh.hip", "layernorm.hip",
            "elementwise.hip", "loss_optim.hip", "adafactor.hip", "dropout.hip"]
 DISTILL_SOURCES = ["distill.hip"]
+LIB_EVAL = os.path.join(HERE, "libbveval.so")         # the classification evaluator's kernel: a library of its own (include/bveval.h)
+EVAL_SOURCES = ["eval.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
          "-DNDEBUG"]
 MAX_JOBS = 16   # compiler processes in flight at once
 INCLUDE = os.path.join(HERE, "..", "include")
-LIBS = [(LIB, SOURCES), (LIB_DISTILL, DISTILL_SOURCES)]
+LIBS = [(LIB, SOURCES), (LIB_DISTILL, DISTILL_SOURCES), (LIB_EVAL, EVAL_SOURCES)]
 
 
 def _headers():
   return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-      os.path.join(INCLUDE, "bvhip.h"), os.path.join(INCLUDE, "bvdistill.h")]
+      os.path.join(INCLUDE, "bvhip.h"), os.path.join(INCLUDE, "bvdistill.h"), os.path.join(INCLUDE, "bveval.h")]
 
 
 def _stale():
@@ -40,17 +42,17 @@ def _stale():
 
 
 def build(force=False, verbose=True):
-  """Compiles what is stale and links both libraries; returns the path of libbvhip.so."""
+  """Compiles what is stale and links every library of LIBS; returns the path of libbvhip.so."""
   hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
   if not force and not _stale():
     return LIB
   if not os.path.exists(hipcc):
-    raise RuntimeError("hipcc not found: cannot build libbvhip.so / libbvdistill.so")
+    raise RuntimeError("hipcc not found: cannot build libbvhip.so / libbvdistill.so / libbveval.so")
   objdir = os.path.join(HERE, "build")
   os.makedirs(objdir, exist_ok=True)
   hdr_t = max(os.path.getmtime(h) for h in _headers())
   todo = []
-  for src in SOURCES + DISTILL_SOURCES:
+  for src in [src for _, sources in LIBS for src in sources]:
     obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
     # per-object staleness: only the sources that changed (or everything, after a header edit)
     if (not force and os.path.exists(obj) and
@@ -84,4 +86,4 @@ def build(force=False, verbose=True):
 
 if __name__ == "__main__":
   build(force="--force" in sys.argv)
-  print("built", LIB, LIB_DISTILL)
+  print("built", *[lib for lib, _ in LIBS])

@@ -743,3 +743,28 @@ def distill_softmax_acc(logits, weight=1.0, probs=None):
     probs = torch.empty_like(logits)
   _lib.call("bv_distill_softmax_acc", _p(logits), _p(probs), float(weight), int(accumulate), n, C, _stream())
   return probs
+
+
+# ---- libbveval.so (include/bveval.h): one batch of the classification evaluator in one launch
+def eval_classify(loss_name, logits, labels, mask=None, acc=None, per_row=False):
+  """One launch of bv_eval_classify on fp32 [n, C] logits and labels (evaluators/classification.py:37-53): acc (f64[3],
+  created when None) += (ncorrect, sum of masked losses, nseen) with mask [n] (None = ones) times the row maximum of
+  the labels as the weight of a row.  Returns acc, or (acc, row_loss f32[n], row_top1 i32[n]) with per_row=True: the
+  unmasked per-example losses and the argmax columns.  An unknown loss_name raises AttributeError, like the
+  reference's `getattr(u, loss_name)`."""
+  if loss_name not in _lib.EVAL_LOSSES:
+    raise AttributeError(f"module 'big_vision.utils' has no loss '{loss_name}' on the evaluation kernel "
+                         f"(available: {sorted(_lib.EVAL_LOSSES)})")
+  n, C = _logits2d(logits, "eval_classify.logits")
+  assert _logits2d(labels, "eval_classify.labels") == (n, C), "logits and labels differ in shape"
+  if mask is not None:
+    _chk(mask, F32, "eval_classify.mask")
+    assert mask.shape == (n,) and mask.is_contiguous(), "eval_classify.mask: expected contiguous fp32 [n]"
+  if acc is None:
+    acc = torch.zeros(3, device=logits.device, dtype=torch.float64)
+  assert acc.dtype == torch.float64 and acc.shape == (3,) and acc.is_contiguous(), "eval_classify.acc: expected f64 [3]"
+  rows = torch.empty((n,), device=logits.device, dtype=F32) if per_row else None
+  top1 = torch.empty((n,), device=logits.device, dtype=torch.int32) if per_row else None
+  _lib.call("bv_eval_classify", _lib.EVAL_LOSSES[loss_name], _p(logits), _p(labels), _p(mask), _p(acc), _p(rows),
+            _p(top1), n, C, _stream())
+  return (acc, rows, top1) if per_row else acc

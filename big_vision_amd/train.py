@@ -179,6 +179,23 @@ def make_update_fn(model, config, comm=None):
   return update_fn
 
 
+def make_predict_fn(model, config=None):
+  """`predict_fn(train_state, batch) -> (logits, out)` (`eval_logits_fn`, train.py:380-382): the forward at train=False on the same
+  kernels as the training step, for `evaluators.common.from_config(config, {"predict": predict_fn})`.  With `config`
+  the forward runs on `config.residual_stream`, like `update_fn`; it reads the parameters and changes nothing."""
+  stream = config.get("residual_stream", "float32") if config is not None else None
+
+  def predict_fn(train_state, batch):
+    old = E.set_residual_stream(stream) if stream is not None else None
+    try:
+      logits, out = model.apply({"params": train_state["params"]}, batch["image"].to(F32).contiguous())
+    finally:
+      if stream is not None:
+        E.set_residual_stream(old)
+    return logits, out
+  return predict_fn
+
+
 def check_finite(measurements):
   """NaN/Inf abort of train.py:452-454 (synchronises)."""
   for k, v in measurements.items():

@@ -32,8 +32,12 @@
 // lane ends up with 16 CONTIGUOUS output columns per row (32/64-byte stores).
 // !KM: half-tile = [64 k][128 rows] in natural order (256 B per k-row); 32-B slot q
 // of k-row k lives at slot q ^ swzk(k); fragments come out of ds_read_b64_tr_b16.
+//
+// Which instantiation serves a call, its grid, split-K factor, slab / atomics combine, start skew and tile order are
+// decided by gemm_route.h; the host code at the end of this file only launches what the route names.
 #include "bv_common.h"
-#include "bvhip_internal.h"
+#include "gemm_call.h"
+#include <climits>
 #include <type_traits>
 
 namespace {
@@ -1400,122 +1404,61 @@ __global__ __launch_bounds__(256) void gemm256_reduce_kernel(const float* __rest
 
 }  // namespace
 
-// Bytes of split-K scratch a dW GEMM (a_kmajor = b_kmajor = 0, EPI_ATOMIC) of this shape uses
-// with the automatic split choice; 0 = the shape takes no workspace.
+// Bytes of split-K scratch the dW GEMM (a_kmajor = b_kmajor = 0, EPI_ATOMIC, fp32 out, aligned operands) of this shape
+// takes with the automatic split choice: the route's slab_bytes under the default options; 0 = the shape takes no
+// workspace.  Exact at gemm_reserve_cus = 0; an upper bound for any other value (fewer CUs in use: the first guess of
+// the split count shrinks, and the final count is monotone in it).
 extern "C" long bv_gemm_workspace_bytes(int M, int N, int K) {
-  if ((M & 255) || (N & 255) || (K & 63)) return 0;
-  const int ntiles = (M >> 8) * (N >> 8), nk = K >> 6;
-  int splits = 256 / (ntiles > 0 ? ntiles : 1);
-  const int max_splits = nk / 8 > 0 ? nk / 8 : 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  const int per = (nk + splits - 1) / splits;
-  splits = (nk + per - 1) / per;
-  return splits > 1 ? (long)ntiles * splits * 65536 * 4 : 0;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  bvgemm::GemmCall c{};
+  c.M = M; c.N = N; c.K = K; c.lda = M; c.ldb = c.ldc = N;
+  c.epilogue = BV_EPI_ATOMIC; c.out_f32 = c.alpha_is_one = true;
+  bvgemm::GemmOpts o = bvgemm::gemm_default_opts();
+  o.has_ws = true; o.ws_bytes = LONG_MAX;
+  return bvgemm::gemm_route(c, o).slab_bytes;
 }
 
-// Internal entry used by bv_gemm_bf16 (gemm_bf16.hip).  Returns 1 if the problem
-// was launched on the 256x256 path, 0 if it does not qualify (caller falls back).
-int bv_gemm256_try(int a_kmajor, int b_kmajor, const void* A, long lda, const void* B, long ldb,
-                   void* C, long ldc, int out_f32, int M, int N, int K, int epilogue,
-                   const float* bias, const void* aux, long ldaux, int aux_rows, void* C2,
-                   float alpha, int split_k, float* colsum, void* stream, const bv_ctx* ctx_) {
-  // every option, the split-K workspace and the launch counters come from the caller's context (NULL: defaults)
-  const bv_ctx* ctx = bv_ctx_or_default(ctx_);
-  const int g_reserve = (int)ctx->opt[BV_OPT_GEMM_RESERVE_CUS], g_roll = (int)ctx->opt[BV_OPT_GEMM_ROLL];
-  const int g_skew_pct = (int)ctx->opt[BV_OPT_GEMM_SKEW_PCT], g_skew_mode = (int)ctx->opt[BV_OPT_GEMM_SKEW_MODE];
-  if (a_kmajor != b_kmajor) return 0;
-  if ((M & 255) || (N & 255) || (K & 63)) return 0;
-  const bool km = a_kmajor != 0;
-  if (km && epilogue == BV_EPI_ATOMIC) return 0;
-  if (!km && !(epilogue == BV_EPI_ATOMIC || (epilogue == BV_EPI_NONE && out_f32 && !bias))) return 0;
-  if ((lda & 7) || (ldb & 7) || (ldc & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) ||
-      ((uintptr_t)C & 15))
-    return 0;
-  if (aux && ((ldaux & 7) || ((uintptr_t)aux & 15))) return 0;
-  if (bias && ((uintptr_t)bias & 15)) return 0;
-  if (C2 && ((uintptr_t)C2 & 15)) return 0;
-
+// See gemm_call.h.  Which kernel, grid, split count and tile order: gemm_route.h.
+int bv_gemm256_launch(const bv_gemm_args& g, const bvgemm::GemmRoute& r, const bv_ctx* ctx) {
+  using namespace bvgemm;   // (the split-K workspace and the launch counters are the caller's context's)
   G256Params p;
-  p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C; p.C2 = C2;
-  p.bias = bias; p.aux = aux; p.colsum = colsum;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux;
-  p.M = M; p.N = N; p.K = K; p.aux_rows = aux_rows > 0 ? aux_rows : 1;
-  p.epi = epilogue; p.out_f32 = out_f32; p.alpha = alpha;
-  const int tiles_m = M >> 8;
-  p.tiles_n = N >> 8;
-  p.ntiles = tiles_m * p.tiles_n;
-  const int nk = K >> 6;
-  int splits = 1;
-  p.slab = nullptr;
-  if (epilogue == BV_EPI_ATOMIC) {
-    // split-K so that tiles x splits ~ one workgroup per CU (256): the K loop is the
-    // whole cost, every extra split adds a 256 KiB partial tile of output traffic.
-    if (split_k > 0) {
-      splits = split_k;
-    } else {
-      splits = (256 - g_reserve) / p.ntiles;   // work items <= CUs in use (4 reserved CUs keep B/16's choices: 252 = 36 x 7 = 9 x 28)
-      const int max_splits = nk / 8 > 0 ? nk / 8 : 1;
-      if (splits > max_splits) splits = max_splits;
-    }
-    if (splits < 1) splits = 1;
-    if (splits > nk) splits = nk;
-  }
-  p.ktiles_per_split = (nk + splits - 1) / splits;
-  splits = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-  const long slab_bytes = (long)p.ntiles * splits * 65536 * 4;
-  void* const ws_ptr = epilogue == BV_EPI_ATOMIC ? ctx->ws : nullptr;
-  const bool use_slab = epilogue == BV_EPI_ATOMIC && splits > 1 && ws_ptr && slab_bytes <= ctx->ws_bytes &&
-                        (ldc & 3) == 0;
-  if (use_slab) p.slab = (float*)ws_ptr;
-  p.splits = splits;
-  const int nwork = p.ntiles * splits;
-  // start skew (see kernel): a percentage of one tile period (~3600 cycles per K-tile + epilogue)
-  p.skew_cycles = 0;
-  p.skew_mode = 0;
-  if (km && g_skew_pct > 0 && nwork > 256) {
-    p.skew_cycles = (int)((long)(nk * 3600 + 12000) * g_skew_pct / 100);
-    p.skew_mode = g_skew_mode;
-  }
-  p.nt = (int)ctx->opt[BV_OPT_GEMM_NT];
-  p.group_n = km ? (int)ctx->opt[BV_OPT_GEMM_GROUP_N] : 0;
-  p.pre_issue = (int)ctx->opt[BV_OPT_GEMM_PRE_ISSUE];
+  bv_gemm_fill(p, g);
+  p.tiles_n = g.N >> 8;
+  p.ntiles = (g.M >> 8) * p.tiles_n;
+  p.splits = r.splits; p.ktiles_per_split = r.ktiles_per_split;
+  p.slab = r.use_slab ? (float*)ctx->ws : nullptr;
+  p.skew_cycles = r.skew_cycles; p.skew_mode = r.skew_mode;
+  p.nt = r.nt; p.group_n = r.group_n; p.pre_issue = r.pre_issue;
   p.dbg = nullptr;
-  const int cus = 256 - g_reserve;
-  dim3 grid(nwork < cus ? nwork : cus), block(512);   // persistent: one workgroup per CU
-  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(r.grid.x), block(r.block);
+  hipStream_t s = (hipStream_t)g.stream;
+#define G256_CASE(name, ...) case name: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, p); break
+  switch (r.kernel) {
+    G256_CASE(G256R_RESIDUAL_F32, gemm256r_kernel<BV_EPI_RESIDUAL, true>);
+    G256_CASE(G256R_GELU_ST, gemm256r_kernel<BV_EPI_GELU, false, 1>);
+    G256_CASE(G256R_GELU, gemm256r_kernel<BV_EPI_GELU, false>);
+    G256_CASE(G256R_NONE_ST, gemm256r_kernel<BV_EPI_NONE, false, 1>);
+    G256_CASE(G256R_NONE, gemm256r_kernel<BV_EPI_NONE, false>);
+    G256_CASE(G256_KMINOR, gemm256_kernel<false>);
+    G256_CASE(G256_RESIDUAL_BF16, gemm256_kernel<true, 0, BV_EPI_RESIDUAL, false>);
+    G256_CASE(G256_RESIDUAL_F32, gemm256_kernel<true, 0, BV_EPI_RESIDUAL, true>);
+    G256_CASE(G256_POS, gemm256_kernel<true, 0, BV_EPI_POS, true>);
+    G256_CASE(G256_GELU, gemm256_kernel<true, 0, BV_EPI_GELU, false>);
+    G256_CASE(G256_GELU_G, gemm256_kernel<true, 0, BV_EPI_GELU_G, false>);
+    G256_CASE(G256_GELU_BWD, gemm256_kernel<true, 0, BV_EPI_GELU_BWD, false>);
+    G256_CASE(G256_GELU_BWD_EMIT, gemm256_kernel<true, 0, BV_EPI_GELU_BWD_EMIT, false>);
+    G256_CASE(G256_GELU_GD, gemm256_kernel<true, 0, BV_EPI_GELU_GD, false>);
+    G256_CASE(G256_MUL, gemm256_kernel<true, 0, BV_EPI_MUL, false>);
+    G256_CASE(G256_NONE_F32, gemm256_kernel<true, 0, BV_EPI_NONE, true>);
+    G256_CASE(G256_NONE_BF16, gemm256_kernel<true, 0, BV_EPI_NONE, false>);
+    default: BV_REQUIRE(false, "bv_gemm_bf16: route names kernel %d, which is not a 256x256 kernel", (int)r.kernel);
+  }
+#undef G256_CASE
   ctx->calls[0].fetch_add(1, std::memory_order_relaxed);
-  if (nwork > (int)grid.x) {
-    ctx->calls[1].fetch_add(1, std::memory_order_relaxed);
-    if ((epilogue != BV_EPI_NONE && epilogue != BV_EPI_ATOMIC) || colsum) ctx->calls[2].fetch_add(1, std::memory_order_relaxed);
-  }
-  // rolling-epilogue kernel: k-major, at least two K-tiles per tile, the epilogues it implements
-  const bool roll = km && nk >= 2 && !colsum &&
-                    (((g_roll & 2) && epilogue == BV_EPI_NONE && !out_f32) ||
-                     ((g_roll & 4) && epilogue == BV_EPI_GELU && !out_f32) ||
-                     ((g_roll & 1) && epilogue == BV_EPI_RESIDUAL && out_f32 && alpha == 1.0f));
-  if (roll) {
-    if (epilogue == BV_EPI_RESIDUAL) hipLaunchKernelGGL((gemm256r_kernel<BV_EPI_RESIDUAL, true>), grid, block, 0, s, p);
-    else if (epilogue == BV_EPI_GELU && (g_roll & 8)) hipLaunchKernelGGL((gemm256r_kernel<BV_EPI_GELU, false, 1>), grid, block, 0, s, p);
-    else if (epilogue == BV_EPI_GELU) hipLaunchKernelGGL((gemm256r_kernel<BV_EPI_GELU, false>), grid, block, 0, s, p);
-    else if (g_roll & 8) hipLaunchKernelGGL((gemm256r_kernel<BV_EPI_NONE, false, 1>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256r_kernel<BV_EPI_NONE, false>), grid, block, 0, s, p);
-    return 1;
-  }
-  if (!km) hipLaunchKernelGGL((gemm256_kernel<false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_RESIDUAL && !out_f32) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_RESIDUAL, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_RESIDUAL) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_RESIDUAL, true>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_POS) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_POS, true>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_GELU) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_GELU, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_GELU_G) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_GELU_G, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_GELU_BWD) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_GELU_BWD, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_GELU_BWD_EMIT) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_GELU_BWD_EMIT, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_GELU_GD) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_GELU_GD, false>), grid, block, 0, s, p);
-  else if (epilogue == BV_EPI_MUL) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_MUL, false>), grid, block, 0, s, p);
-  else if (out_f32) hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_NONE, true>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((gemm256_kernel<true, 0, BV_EPI_NONE, false>), grid, block, 0, s, p);
-  if (use_slab)
-    hipLaunchKernelGGL(gemm256_reduce_kernel, dim3(p.ntiles * 64), dim3(256), 0, s, (const float*)ws_ptr,
-                       (float*)C, ldc, p.ntiles, p.tiles_n, splits, alpha, 1);
-  return 1;
+  if (r.multi) ctx->calls[1].fetch_add(1, std::memory_order_relaxed);
+  if (r.fused) ctx->calls[2].fetch_add(1, std::memory_order_relaxed);
+  if (r.use_slab)
+    hipLaunchKernelGGL(gemm256_reduce_kernel, dim3(p.ntiles * 64), dim3(256), 0, s, (const float*)ctx->ws, (float*)g.C,
+                       g.ldc, p.ntiles, p.tiles_n, r.splits, g.alpha, 1);
+  return BV_OK;
 }

@@ -18,8 +18,12 @@
 // The MFMA is issued "swapped" (first operand = B rows, second = A rows) so a
 // lane ends up with 4 consecutive output columns of one output row, giving 8/16
 // byte epilogue accesses.
+//
+// bv_gemm_bf16_colsum at the end of this file is the entry point of every bf16 GEMM: it validates the call, asks
+// gemm_route.h which kernel serves it (this file's, or gemm256.hip's 256x256 family), on what grid and with how many K
+// splits, and hands the route to that family's launcher.
 #include "bv_common.h"
-#include "bvhip_internal.h"
+#include "gemm_call.h"
 
 namespace {
 
@@ -283,13 +287,21 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
   }
 }
 
-}  // namespace
+// Launches a route of the family GEMM_128 (gemm_route.h)
+void gemm128_launch(const bv_gemm_args& g, const bvgemm::GemmRoute& r) {
+  using namespace bvgemm;
+  GemmParams p;
+  bv_gemm_fill(p, g);
+  p.k_chunk = r.k_chunk;
+  const dim3 grid(r.grid.x, r.grid.y, r.grid.z), block(r.block);
+  hipStream_t s = (hipStream_t)g.stream;
+  if (r.kernel == G128_A1B1) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, 0, s, p);
+  else if (r.kernel == G128_A1B0) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, 0, s, p);
+  else if (r.kernel == G128_A0B0) hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, block, 0, s, p);
+}
 
-// gemm256.hip
-int bv_gemm256_try(int a_kmajor, int b_kmajor, const void* A, long lda, const void* B, long ldb,
-                   void* C, long ldc, int out_f32, int M, int N, int K, int epilogue,
-                   const float* bias, const void* aux, long ldaux, int aux_rows, void* C2,
-                   float alpha, int split_k, float* colsum, void* stream, const bv_ctx* ctx);
+}  // namespace
 
 // See include/bvhip.h for the contract.
 extern "C" int bv_gemm_bf16_colsum(int a_kmajor, int b_kmajor, const void* A, long lda, const void* B,
@@ -334,45 +346,15 @@ extern "C" int bv_gemm_bf16_colsum(int a_kmajor, int b_kmajor, const void* A, lo
     BV_REQUIRE(epilogue == BV_EPI_GELU_BWD || epilogue == BV_EPI_GELU_BWD_EMIT || epilogue == BV_EPI_MUL,
                "bv_gemm_bf16_colsum: column sums are fused into the GELU_BWD / MUL epilogues only (got %d)", epilogue);
 
-  if (bv_opt(ctx, BV_OPT_FAST_PATH) &&
-      bv_gemm256_try(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, out_f32, M, N, K, epilogue, bias, aux, ldaux, aux_rows,
-                     C2, alpha, split_k, colsum, stream, ctx))
-    return bv_check_launch("bv_gemm_bf16(256x256)");
-
-  GemmParams p;
-  p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C; p.C2 = C2;
-  p.bias = bias; p.aux = aux; p.colsum = colsum;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux;
-  p.M = M; p.N = N; p.K = K; p.aux_rows = aux_rows > 0 ? aux_rows : 1;
-  p.epi = epilogue; p.out_f32 = out_f32; p.alpha = alpha;
-
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  int splits = 1;
-  if (epilogue == BV_EPI_ATOMIC) {
-    const int ksteps = (K + BK - 1) / BK;
-    if (split_k > 0) {
-      splits = split_k;
-    } else {
-      // aim for >= 1024 workgroups (256 CUs x 2 resident x 2 waves of work)
-      // while keeping >= 8 K-steps per split.
-      splits = (1024 + tiles_m * tiles_n - 1) / (tiles_m * tiles_n);
-      const int max_splits = ksteps / 8 > 0 ? ksteps / 8 : 1;
-      if (splits > max_splits) splits = max_splits;
-    }
-    if (splits < 1) splits = 1;
-    if (splits > ksteps) splits = ksteps;
-    const int steps_per = (ksteps + splits - 1) / splits;
-    p.k_chunk = steps_per * BK;
-    splits = (K + p.k_chunk - 1) / p.k_chunk;
-  } else {
-    p.k_chunk = ((K + BK - 1) / BK) * BK;
+  const bv_gemm_args g{a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, out_f32, M, N, K, epilogue, bias, aux, ldaux, aux_rows, C2,
+                       alpha, split_k, colsum, stream};
+  const bv_ctx* const cx = bv_ctx_or_default(ctx);
+  const bvgemm::GemmRoute r = bv_gemm_route(g, cx);
+  if (r.family != bvgemm::GEMM_128) {
+    const int rc = bv_gemm256_launch(g, r, cx);
+    return rc != BV_OK ? rc : bv_check_launch("bv_gemm_bf16(256x256)");
   }
-  BV_REQUIRE(tiles_m <= 65535 && splits <= 65535, "bv_gemm_bf16: grid too large");
-  dim3 grid(tiles_n, tiles_m, splits), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, 0, s, p);
-  else if (a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, 0, s, p);
-  else if (!a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, block, 0, s, p);
+  BV_REQUIRE(r.grid.y <= 65535 && r.grid.z <= 65535, "bv_gemm_bf16: grid too large");
+  gemm128_launch(g, r);
   return bv_check_launch("bv_gemm_bf16");
 }

@@ -55,8 +55,9 @@ void bv_ctx_destroy(bv_ctx* ctx);
 /* Options (diagnostics / A-B benchmarking; defaults in parentheses; results never depend on them
  * beyond the summation order of a different kernel). */
 #define BV_OPT_FAST_PATH 0         /* (1) GEMMs with M, N multiples of 256, K of 64 and both operands in the same
-                                      layout run on the 256x256x64 direct-to-LDS kernel; 0: everything on the
-                                      general 128x128x64 kernel */
+                                      layout run on the 256x256x64 direct-to-LDS kernel (pitches multiples of 8, every
+                                      pointer 16-byte aligned; k-major: every epilogue but ATOMIC, k-minor: ATOMIC, or
+                                      NONE with fp32 out and no bias); 0: everything on the general 128x128x64 kernel */
 #define BV_OPT_GEMM_NT 1           /* (0) bit 0 = streaming (nontemporal) stores of C / C2, bit 1 = streaming aux loads */
 #define BV_OPT_GEMM_SKEW_MODE 2    /* (1) start phase per XCD (0) / per workgroup (1), see SKEW_PCT */
 #define BV_OPT_GEMM_SKEW_PCT 3     /* (0) spread of the persistent workgroups' start, % of one tile period */
@@ -96,7 +97,8 @@ long bv_ctx_get(const bv_ctx* ctx, int opt);
  * weight-gradient GEMMs (EPI_ATOMIC) launched through this context: with a workspace the partials are written
  * with plain coalesced stores and combined by a second small kernel (deterministic); without one (no context, or
  * ptr = NULL) fp32 atomics are used.  bv_gemm_workspace_bytes(M, N, K) = bytes the dW GEMM C[M,N] = A[K,M]^T B[K,N]
- * takes with the automatic split choice (0: the shape needs none) -- size the slab for the largest. */
+ * takes with the automatic split choice (0: the shape needs none) -- size the slab for the largest.  Exact at
+ * BV_OPT_GEMM_RESERVE_CUS = 0, an upper bound for any other value (fewer CUs in use never raise the split count). */
 int bv_ctx_set_workspace(bv_ctx* ctx, void* ptr, long bytes);
 long bv_gemm_workspace_bytes(int M, int N, int K);
 

@@ -34,6 +34,7 @@ pytestmark = pytest.mark.gpu
 BF16, F32, F64, I32, U8 = torch.bfloat16, torch.float32, torch.float64, torch.int32, torch.uint8
 
 ROWS = []   # (entry points covered, case id, fn(dev))
+ARGS = {}   # case id -> (row function, args, kw) of the rows made by add(): test_gemm_route_cpu.py reads the GEMM rows
 
 
 def row(entries, case):
@@ -45,6 +46,7 @@ def row(entries, case):
 
 def add(entries, case, fn, *args, **kw):
   ROWS.append((tuple(entries.split()), case, lambda dev: fn(dev, *args, **kw)))
+  ARGS[case] = (fn, args, kw)
 
 
 def stream():

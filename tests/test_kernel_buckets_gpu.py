@@ -11,7 +11,7 @@ dispatchers without running anything:
   layernorm.hip   bv_layernorm_fwd / _bwd_y: NV = 3 (D <= 768) / 4 (<= 1024) / 8, NT = ln_nt_for (rows * D * 4 > 192 MiB);
                   bv_layernorm_bwd_bf16x: bf16 dy -> ln_bwd_bfx2_kernel<nv4 = 3/4/5/8, FULL = D == NV * 256, RES>,
                   fp32 dy -> ln_bwd_bfx_kernel<true, D <= 1024 ? 2 : 4>; bv_layernorm_fwd_bf16x NV = 3/4/5/8
-  gemm_bf16.hip   gemm_bf16_kernel<A_KM, B_KM> when bv_gemm256_try declines (gemm256.hip: M, N % 256, K % 64, same layout)
+  gemm_bf16.hip   gemm_bf16_kernel<A_KM, B_KM> where csrc/gemm_route.h gives the call to GEMM_128 (GEMM_256: M, N % 256, K % 64, same layout)
   gemm256.hip     gemm256r_kernel<EPI, F32, 1> under BV_OPT_GEMM_ROLL bit 8
 
 Tolerances are those of the same family in test_kernels_gpu.py: attention o 2e-2, lse 1e-4 / 1e-3, dqkv the backward model of
@@ -358,7 +358,7 @@ EDGES = [(512, 768, 128, True), (504, 768, 128, False), (520, 768, 128, False), 
 @pytest.mark.parametrize("M,N,K,fast", [pytest.param(*e, id=f"M{e[0]}-N{e[1]}-K{e[2]}-{'gemm256' if e[3] else 'general'}")
                                         for e in EDGES])
 def test_gemm_fast_path_edges(dev, M, N, K, fast):
-  """bv_gemm256_try accepts exactly M, N % 256 == 0 and K % 64 == 0 (its launch counter moves); both sides vs fp32 on
+  """csrc/gemm_route.h gives the 256 x 256 kernels exactly M, N % 256 == 0 and K % 64 == 0 (their launch counter moves); both sides vs fp32 on
   the same bf16 inputs, the accepted one also vs the general kernel, for the k-major forward / dX layout and the
   k-minor dW layout (fp32 atomic accumulation)."""
   from big_vision_amd import ops

@@ -1,6 +1,6 @@
 // Round-3 GEMM probe (standalone, no torch):
 //   (1) every epilogue variant of the 256x256 k-major kernel on the training step's shapes, through the
-//       library's own dispatcher (bv_gemm256_try): TFLOP/s per shape and epilogue - in particular the
+//       library's own dispatch (csrc/gemm_route.h through probe_gemm256): TFLOP/s per shape and epilogue - in particular the
 //       forward GELU pair (BV_EPI_GELU vs BV_EPI_GELU_GD) and the backward trio (GELU_BWD / _EMIT / MUL);
 //   (2) the main loop with v_mfma_f32_32x32x16_bf16 (PROBE 11: same LDS images, DMA ring, barriers and
 //       register counts, 8 MFMAs of 32x32x16 per phase instead of 16 of 16x16x32; results are garbage, the
@@ -16,6 +16,7 @@
 #define BV_GEMM256_PROBES   // compiles the PROBE != 0 ablation paths of gemm256_kernel (absent from the library build)
 #include "../../big_vision_amd/csrc/gemm256.hip"
 #include "probe_ctx.h"
+#include "probe_gemm256.h"
 
 __global__ void fill_bf16(unsigned short* d, size_t n, unsigned seed, float scale) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -96,7 +97,7 @@ int main(int argc, char** argv) {
     const int it = s.M > 200000 ? 4 : 8;
     auto tf = [&](int epi, int f32, const void* aux, void* c2, float* cs) {
       auto run = [&] {
-        const int ok = bv_gemm256_try(1, 1, a, s.K, b, s.K, c0, s.N, f32, s.M, s.N, s.K, epi, bias, aux, s.N, 0, c2, 1.0f, 0, cs, nullptr, probe_ctx());
+        const int ok = probe_gemm256(1, 1, a, s.K, b, s.K, c0, s.N, f32, s.M, s.N, s.K, epi, bias, aux, s.N, 0, c2, 1.0f, 0, cs, nullptr, probe_ctx());
         if (!ok) { printf("not dispatched\n"); exit(1); }
       };
       float t = 1e30f;

@@ -1,5 +1,5 @@
 // A/B of the rolling-epilogue kernel (gemm256r_kernel) against gemm256_kernel<true> through the
-// library's own dispatcher (bv_gemm256_try with bv_gemm_roll(0/1)): bit-exactness for the bf16
+// library's own dispatch (probe_gemm256 with bv_gemm_roll(0/1)): bit-exactness for the bf16
 // epilogues (same accumulation order, same epilogue arithmetic), max-abs difference for the
 // residual epilogue (the residual is summed first instead of last), run-to-run bit-equality of the
 // new kernel (race screen) and timing of both on the training step's shapes.
@@ -14,6 +14,7 @@
 #define BV_GEMM256_PROBES   // compiles the PROBE != 0 ablation paths of gemm256_kernel (absent from the library build)
 #include "../../big_vision_amd/csrc/gemm256.hip"
 #include "probe_ctx.h"
+#include "probe_gemm256.h"
 
 __global__ void fill_bf16(unsigned short* d, size_t n, unsigned seed, float scale) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -120,7 +121,7 @@ int main(int argc, char** argv) {
     const size_t cbytes = (size_t)s.M * ldc * (f32 ? 4 : 2);
     auto run = [&](int roll, void* c, void* c2) {
       bv_gemm_roll(roll ? mask : 0);
-      const int ok = bv_gemm256_try(1, 1, a, s.K, b, s.K, c, ldc, f32 ? 1 : 0, s.M, s.N, s.K, s.epi, bias,
+      const int ok = probe_gemm256(1, 1, a, s.K, b, s.K, c, ldc, f32 ? 1 : 0, s.M, s.N, s.K, s.epi, bias,
                                     f32 ? aux : nullptr, s.N, 0, s.epi == BV_EPI_GELU ? c2 : nullptr, 1.0f, 0,
                                     nullptr, nullptr, probe_ctx());
       if (!ok) { printf("%s: not dispatched to the 256x256 path\n", s.name); exit(1); }

@@ -16,6 +16,7 @@
 #define BV_GEMM256_PROBES   // compiles the PROBE != 0 ablation paths of gemm256_kernel (absent from the library build)
 #include "../../big_vision_amd/csrc/gemm256.hip"
 #include "probe_ctx.h"
+#include "probe_gemm256.h"
 
 __global__ void fill_bf16(unsigned short* d, size_t n, unsigned seed, float scale) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -210,7 +211,7 @@ int main() {
     RowParams p{(const bf16*)a, (const bf16*)b, (bf16*)c1, s.K, s.K, N, s.M, s.K, s.M / 128};
     const int grid = p.ntiles < 256 ? p.ntiles : 256;
     auto ref = [&]() {
-      if (!bv_gemm256_try(1, 1, a, s.K, b, s.K, c0, N, 0, s.M, N, s.K, BV_EPI_NONE, nullptr, nullptr, 0, 0, nullptr, 1.0f, 0, nullptr,
+      if (!probe_gemm256(1, 1, a, s.K, b, s.K, c0, N, 0, s.M, N, s.K, BV_EPI_NONE, nullptr, nullptr, 0, 0, nullptr, 1.0f, 0, nullptr,
                           nullptr, probe_ctx())) { printf("ref not dispatched\n"); exit(1); }
     };
     ref(); run_row<0>(p, grid);

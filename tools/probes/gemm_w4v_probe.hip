@@ -31,6 +31,7 @@
 #define BV_GEMM256_PROBES   // compiles the PROBE != 0 ablation paths of gemm256_kernel (absent from the library build)
 #include "../../big_vision_amd/csrc/gemm256.hip"
 #include "probe_ctx.h"
+#include "probe_gemm256.h"
 
 namespace {
 
@@ -279,7 +280,7 @@ int main() {
     W4Params p{(const bf16*)a, (const bf16*)b, (bf16*)c1, s.K, s.K, s.N, s.M, s.N, s.K, s.N / 256, (s.M / 256) * (s.N / 256)};
     const int grid = p.ntiles < 256 ? p.ntiles : 256;
     auto ref = [&]() {
-      if (!bv_gemm256_try(1, 1, a, s.K, b, s.K, c0, s.N, 0, s.M, s.N, s.K, BV_EPI_NONE, nullptr, nullptr, 0, 0, nullptr, 1.0f,
+      if (!probe_gemm256(1, 1, a, s.K, b, s.K, c0, s.N, 0, s.M, s.N, s.K, BV_EPI_NONE, nullptr, nullptr, 0, 0, nullptr, 1.0f,
                           0, nullptr, nullptr, probe_ctx())) { printf("ref not dispatched\n"); exit(1); }
     };
     auto w4 = [&]() { hipLaunchKernelGGL(gemm_w4v_kernel, dim3(grid), dim3(256), 0, 0, p); };

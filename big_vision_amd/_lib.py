@@ -1,5 +1,6 @@
-"""ctypes binding of libbvhip.so (the C ABI declared in include/bvhip.h), of libbvdistill.so (include/bvdistill.h) and
-of libbveval.so (include/bveval.h).
+"""ctypes binding of the kernel libraries of build.LIBS: libbvhip.so (the C ABI declared in include/bvhip.h),
+libbvdistill.so (include/bvdistill.h) and libbveval.so (include/bveval.h).  One Library record each, one path that
+binds them (`_bind`) and one that calls into them (`call`).
 
 The product path has NO fallback: if the shared library is missing or a call
 fails, a RuntimeError is raised.  Build it with `python big_vision_amd/build.py`
@@ -15,14 +16,11 @@ import torch  # noqa: F401  pylint: disable=unused-import
 
 from ctypes import c_int, c_long, c_float, c_void_p
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libbvhip.so")
-LIB_DISTILL_PATH = os.path.join(_HERE, "libbvdistill.so")
-LIB_EVAL_PATH = os.path.join(_HERE, "libbveval.so")
+from big_vision_amd import build
 
 P = c_void_p
 
-# name -> argtypes (return type is always int, except bv_last_error)
+# libbvhip.so (include/bvhip.h): name -> argtypes (the return type is int unless RESTYPES names another)
 PROTOTYPES = {
     "bv_version": [],
     # the caller's context (options, split-K workspace, launch counters): the library keeps no global state
@@ -87,22 +85,17 @@ PROTOTYPES = {
     "bv_adam_step": [P, P, P, c_int, P, P, P, P, c_long, P, c_int, P, c_float, c_float, c_float,
                      c_float, c_float, c_float, P, P],
     "bv_trace_step": [P, P, P, c_int, P, P, P, c_long, P, c_int, P, c_float, c_float, c_int, P, P],
-}
-
-PROTOTYPES["bv_adafactor_leaf"] = [P, P, P, c_int, P, P, P, c_int, P, c_float, c_float, c_float, c_float,
-                                   c_float, c_float, c_float, P, P]
-
-PROTOTYPES["bv_adafactor_step"] = [P, P, P, c_int, P, P, c_int, c_long, c_long, c_long, c_long, P, P, c_float, c_float,
-                                   c_float, c_float, P, c_int, P, c_float, P, P]
-
-# collectives for non-Python hosts (csrc/comm.cpp; the Python host uses torch.distributed, dp.py)
-PROTOTYPES.update({
+    "bv_adafactor_leaf": [P, P, P, c_int, P, P, P, c_int, P, c_float, c_float, c_float, c_float,
+                          c_float, c_float, c_float, P, P],
+    "bv_adafactor_step": [P, P, P, c_int, P, P, c_int, c_long, c_long, c_long, c_long, P, P, c_float, c_float,
+                          c_float, c_float, P, c_int, P, c_float, P, P],
+    # collectives for non-Python hosts (csrc/comm.cpp; the Python host uses torch.distributed, dp.py)
     "bv_comm_version": [P], "bv_comm_unique_id": [P], "bv_comm_init": [P, c_int, c_int, P], "bv_comm_destroy": [P],
     "bv_comm_all_gather": [P, P, P, c_long, c_int, P], "bv_comm_reduce_scatter": [P, P, P, c_long, c_int, P],
     "bv_comm_all_reduce_bucket": [P, P, c_long, c_long, c_int, P],
-})
+}
 
-# everything else returns an int status
+# the entry points of libbvhip.so that do not return an int status
 RESTYPES = {"bv_gemm_workspace_bytes": c_long, "bv_ctx_create": P, "bv_ctx_destroy": None, "bv_ctx_set": c_long,
             "bv_ctx_get": c_long}
 
@@ -131,83 +124,60 @@ EVAL_LOSSES = {"softmax_xent": 0, "sigmoid_xent": 1}
 
 EPI_NONE, EPI_RESIDUAL, EPI_POS, EPI_GELU, EPI_GELU_BWD, EPI_ATOMIC, EPI_GELU_BWD_EMIT, EPI_GELU_GD, EPI_MUL, EPI_GELU_G = range(10)
 
-_lib = None
-_lib_distill = None
-_lib_eval = None
+
+class Library:
+  """One kernel library: the file and header of its build.LIBS record (`path` may be pointed at another build of the
+  same ABI before the first load()), its prototype table with the restypes that are not int, its last-error and
+  version entry points and the ABI version this binding expects.  `dll` is the bound CDLL, None until load()."""
+
+  def __init__(self, path, header, prototypes, last_error, version_fn, version, restypes=None):
+    self.name, self.path, self.header = os.path.basename(path), path, header
+    self.prototypes, self.restypes = prototypes, restypes or {}
+    self.last_error, self.version_fn, self.version = last_error, version_fn, version
+    self.dll = None
 
 
-def _load_distill():
-  global _lib_distill
-  if not os.path.exists(LIB_DISTILL_PATH):
+_BINDINGS = {
+    "hip": dict(prototypes=PROTOTYPES, restypes=RESTYPES, last_error="bv_last_error", version_fn="bv_version", version=2),
+    "distill": dict(prototypes=PROTOTYPES_DISTILL, last_error="bv_distill_last_error", version_fn="bv_distill_version",
+                    version=1),
+    "eval": dict(prototypes=PROTOTYPES_EVAL, last_error="bv_eval_last_error", version_fn="bv_eval_version", version=1),
+}
+LIBRARIES = {r.key: Library(r.path, r.header, **_BINDINGS[r.key]) for r in build.LIBS}
+_owner = {}   # entry point -> the bound Library that exports it
+
+
+def _bind(d):
+  if not os.path.exists(d.path):
     raise RuntimeError(
-        f"{LIB_DISTILL_PATH} is missing: the HIP extension is not built. Run "
+        f"{d.path} is missing: the HIP extension is not built. Run "
         "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
-  lib = ctypes.CDLL(LIB_DISTILL_PATH)
-  lib.bv_distill_last_error.restype = ctypes.c_char_p
-  lib.bv_distill_last_error.argtypes = []
-  for name, argtypes in PROTOTYPES_DISTILL.items():
-    fn = getattr(lib, name)  # AttributeError if the ABI drifted
-    fn.restype = c_int
+  dll = ctypes.CDLL(d.path)
+  last_error = getattr(dll, d.last_error)
+  last_error.restype = ctypes.c_char_p
+  last_error.argtypes = []
+  for name, argtypes in d.prototypes.items():
+    fn = getattr(dll, name)  # AttributeError if the ABI drifted
+    fn.restype = d.restypes.get(name, c_int)
     fn.argtypes = argtypes
-  if lib.bv_distill_version() != 1:
-    raise RuntimeError("libbvdistill.so ABI version mismatch")
-  _lib_distill = lib
-  return lib
-
-
-def load_distill():
-  """libbvdistill.so (bound by load(), together with libbvhip.so)."""
-  load()
-  return _lib_distill
-
-
-def _load_eval():
-  global _lib_eval
-  if not os.path.exists(LIB_EVAL_PATH):
-    raise RuntimeError(
-        f"{LIB_EVAL_PATH} is missing: the HIP extension is not built. Run "
-        "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
-  lib = ctypes.CDLL(LIB_EVAL_PATH)
-  lib.bv_eval_last_error.restype = ctypes.c_char_p
-  lib.bv_eval_last_error.argtypes = []
-  for name, argtypes in PROTOTYPES_EVAL.items():
-    fn = getattr(lib, name)  # AttributeError if the ABI drifted
-    fn.restype = c_int
-    fn.argtypes = argtypes
-  if lib.bv_eval_version() != 1:
-    raise RuntimeError("libbveval.so ABI version mismatch")
-  _lib_eval = lib
-  return lib
-
-
-def load_eval():
-  """libbveval.so (bound by load(), together with the other two libraries)."""
-  load()
-  return _lib_eval
+  if getattr(dll, d.version_fn)() != d.version:
+    raise RuntimeError(f"{d.name} ABI version mismatch")
+  d.dll = dll
+  _owner.update(dict.fromkeys(d.prototypes, d))
 
 
 def load():
-  """Loads libbvhip.so, libbvdistill.so and libbveval.so (once).  Raises if they are not built — no fallback."""
-  global _lib
-  if _lib is not None:
-    return _lib
-  if not os.path.exists(LIB_PATH):
-    raise RuntimeError(
-        f"{LIB_PATH} is missing: the HIP extension is not built. Run "
-        "`python big_vision_amd/build.py`. There is no CPU/eager fallback.")
-  _load_distill()
-  _load_eval()
-  lib = ctypes.CDLL(LIB_PATH)
-  lib.bv_last_error.restype = ctypes.c_char_p
-  lib.bv_last_error.argtypes = []
-  for name, argtypes in PROTOTYPES.items():
-    fn = getattr(lib, name)  # AttributeError if the ABI drifted
-    fn.restype = RESTYPES.get(name, c_int)
-    fn.argtypes = argtypes
-  if lib.bv_version() != 2:
-    raise RuntimeError("libbvhip.so ABI version mismatch")
-  _lib = lib
-  return lib
+  """Binds every library of LIBRARIES (once) and returns libbvhip.so.  Raises if one is not built — no fallback."""
+  for d in LIBRARIES.values():
+    if d.dll is None:
+      _bind(d)
+  return LIBRARIES["hip"].dll
+
+
+def handle(key):
+  """The bound library of that key ("hip", "distill", "eval"), for calls that bypass `call`."""
+  load()
+  return LIBRARIES[key].dll
 
 
 # Optional launch observer (bench.py installs one to bracket selected kernels
@@ -216,28 +186,18 @@ observer = None
 
 
 def call(name, *args):
-  lib = load()
-  if name in PROTOTYPES_DISTILL:    # routed to the library whose table holds the name
-    return _call_in(_lib_distill, _lib_distill.bv_distill_last_error, name, args)
-  if name in PROTOTYPES_EVAL:
-    return _call_in(_lib_eval, _lib_eval.bv_eval_last_error, name, args)
+  d = _owner.get(name)
+  if d is None:
+    load()
+    d = _owner.get(name)
+    if d is None:
+      raise AttributeError(f"{name}: no library of _lib.LIBRARIES declares it")
   obs = observer
   tok = obs.begin(name, args) if obs is not None else None
-  rc = getattr(lib, name)(*args)
+  rc = getattr(d.dll, name)(*args)
   if tok is not None:
     obs.end(tok)
-  if name in RESTYPES:
+  if name in d.restypes:
     return rc
   if rc != 0:
-    raise RuntimeError(f"{name} failed (rc={rc}): {lib.bv_last_error().decode()}")
-
-
-def _call_in(lib, last_error, name, args):
-  """One call into a library whose every entry point returns an int status; `last_error` is that library's own."""
-  obs = observer
-  tok = obs.begin(name, args) if obs is not None else None
-  rc = getattr(lib, name)(*args)
-  if tok is not None:
-    obs.end(tok)
-  if rc != 0:
-    raise RuntimeError(f"{name} failed (rc={rc}): {last_error().decode()}")
+    raise RuntimeError(f"{name} failed (rc={rc}): {getattr(d.dll, d.last_error)().decode()}")

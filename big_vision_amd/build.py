@@ -9,6 +9,7 @@ ncclComm_t / ncclDataType_t types and the prototypes of the eight entry points i
 is NO link-time RCCL dependency: comm.cpp dlopen()s librccl.so at the first bv_comm_* call, so the
 library loads on hosts without RCCL as long as nothing calls those entry points.
 """
+import collections
 import os
 import shutil
 import subprocess
@@ -16,43 +17,49 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-LIB = os.path.join(HERE, "libbvhip.so")
-LIB_DISTILL = os.path.join(HERE, "libbvdistill.so")   # the distillation losses: a library of its own (include/bvdistill.h)
-SOURCES = ["c_api.cpp", "comm.cpp", "gemm_bf16.hip", "gemm256.hip", "attention.hip", "attention3.hip", "attention5.hip", "attention_dh.hip", "layernorm.hip",
-           "elementwise.hip", "loss_optim.hip", "adafactor.hip", "dropout.hip"]
-DISTILL_SOURCES = ["distill.hip"]
-LIB_EVAL = os.path.join(HERE, "libbveval.so")         # the classification evaluator's kernel: a library of its own (include/bveval.h)
-EVAL_SOURCES = ["eval.hip"]
+INCLUDE = os.path.join(HERE, "..", "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
          "-DNDEBUG"]
 MAX_JOBS = 16   # compiler processes in flight at once
-INCLUDE = os.path.join(HERE, "..", "include")
-LIBS = [(LIB, SOURCES), (LIB_DISTILL, DISTILL_SOURCES), (LIB_EVAL, EVAL_SOURCES)]
+
+# One record per kernel library: its key (big_vision_amd/_lib.py binds by the same key), the shared object, the
+# public header that declares its C ABI and its sources under csrc/.  Everything below iterates this table.
+Lib = collections.namedtuple("Lib", "key path header sources")
+LIBS = [
+    Lib("hip", os.path.join(HERE, "libbvhip.so"), os.path.join(INCLUDE, "bvhip.h"),
+        ["c_api.cpp", "comm.cpp", "gemm_bf16.hip", "gemm256.hip", "attention.hip", "attention3.hip", "attention5.hip",
+         "attention_dh.hip", "layernorm.hip", "elementwise.hip", "loss_optim.hip", "adafactor.hip", "dropout.hip"]),
+    Lib("distill", os.path.join(HERE, "libbvdistill.so"), os.path.join(INCLUDE, "bvdistill.h"), ["distill.hip"]),
+    Lib("eval", os.path.join(HERE, "libbveval.so"), os.path.join(INCLUDE, "bveval.h"), ["eval.hip"]),
+]
+
+
+def lib(key):
+  return next(r for r in LIBS if r.key == key)
 
 
 def _headers():
-  return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-      os.path.join(INCLUDE, "bvhip.h"), os.path.join(INCLUDE, "bvdistill.h"), os.path.join(INCLUDE, "bveval.h")]
+  return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [r.header for r in LIBS]
 
 
 def _stale():
   deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _headers()
   newest = max(os.path.getmtime(d) for d in deps)
-  return any(not os.path.exists(lib) or os.path.getmtime(lib) < newest for lib, _ in LIBS)
+  return any(not os.path.exists(r.path) or os.path.getmtime(r.path) < newest for r in LIBS)
 
 
 def build(force=False, verbose=True):
   """Compiles what is stale and links every library of LIBS; returns the path of libbvhip.so."""
   hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
   if not force and not _stale():
-    return LIB
+    return lib("hip").path
   if not os.path.exists(hipcc):
-    raise RuntimeError("hipcc not found: cannot build libbvhip.so / libbvdistill.so / libbveval.so")
+    raise RuntimeError("hipcc not found: cannot build " + " / ".join(os.path.basename(r.path) for r in LIBS))
   objdir = os.path.join(HERE, "build")
   os.makedirs(objdir, exist_ok=True)
   hdr_t = max(os.path.getmtime(h) for h in _headers())
   todo = []
-  for src in [src for _, sources in LIBS for src in sources]:
+  for src in [src for r in LIBS for src in r.sources]:
     obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
     # per-object staleness: only the sources that changed (or everything, after a header edit)
     if (not force and os.path.exists(obj) and
@@ -75,15 +82,15 @@ def build(force=False, verbose=True):
     running.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
   for src, p in running:
     reap(src, p)
-  for lib, sources in LIBS:
-    objs = [os.path.join(objdir, os.path.splitext(src)[0] + ".o") for src in sources]
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib]
+  for r in LIBS:
+    objs = [os.path.join(objdir, os.path.splitext(src)[0] + ".o") for src in r.sources]
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", r.path]
     if verbose:
       print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-  return LIB
+  return lib("hip").path
 
 
 if __name__ == "__main__":
   build(force="--force" in sys.argv)
-  print("built", *[lib for lib, _ in LIBS])
+  print("built", *[r.path for r in LIBS])

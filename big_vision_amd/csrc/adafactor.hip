@@ -25,14 +25,6 @@ struct AfView {
   long sB1, sB2, sR, sC;
 };
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 __device__ __forceinline__ float clip_factor(const double* gsq, float clip_norm) {
   if (clip_norm <= 0.f) return 1.f;
   const float norm = (float)sqrt(gsq[0]);

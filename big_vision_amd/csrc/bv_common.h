@@ -1,30 +1,15 @@
-// Common device/host helpers for libbvhip (gfx950 / MI355X only).
+// Common device/host helpers of the kernel libraries (gfx950 / MI355X only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "bv_status.h"   // BV_OK / BV_ERR_*, bv_set_error, bv_check_launch, BV_REQUIRE
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define BV_OK 0
-#define BV_ERR_INVALID_ARG (-1)
-#define BV_ERR_UNSUPPORTED (-2)
-#define BV_ERR_HIP (-3)
-
-// Defined in c_api.cpp
-void bv_set_error(const char* fmt, ...);
-int bv_check_launch(const char* what);
-
-#define BV_REQUIRE(cond, ...)                 \
-  do {                                        \
-    if (!(cond)) {                            \
-      bv_set_error(__VA_ARGS__);              \
-      return BV_ERR_INVALID_ARG;              \
-    }                                         \
-  } while (0)
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
@@ -50,6 +35,15 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+// sum over a 256-lane workgroup; sh: 4 words of LDS (the leading barrier lets back-to-back sums share them)
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 // flax nn.gelu(approximate=True): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3), written as

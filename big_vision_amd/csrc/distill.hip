@@ -17,29 +17,11 @@
 // output element is written once.  The register arrays are only ever indexed by the induction variables of fully
 // unrolled loops (compile-time constants): a run-time index would move them to scratch.  C > 4096 re-reads the row in
 // every phase (MODE_STREAM) with the same arithmetic per element, always with 4-byte accesses (an untuned fallback).
-#include <stdarg.h>
-#include <stdio.h>
-
+#define BV_STATUS_LINKAGE static   // the whole library is this file
 #include "bv_common.h"
 #include "../../include/bvdistill.h"
 
-static thread_local char distill_err[512] = "";
-
-static int distill_fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(distill_err, sizeof(distill_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define BVD_REQUIRE(cond, ...) \
-  do {                         \
-    if (!(cond)) return distill_fail(BVD_ERR_INVALID_ARG, __VA_ARGS__); \
-  } while (0)
-
-extern "C" const char* bv_distill_last_error(void) { return distill_err; }
-extern "C" int bv_distill_version(void) { return BVDISTILL_VERSION; }
+BV_DEFINE_STATUS(bv_distill_last_error, bv_distill_version, BVDISTILL_VERSION)
 
 namespace {
 
@@ -351,12 +333,6 @@ int row_mode(int C, const void* a, const void* b, const void* c) {
   return (C % 4 == 0 && aligned16(a) && (!b || aligned16(b)) && (!c || aligned16(c))) ? MODE_VEC : MODE_SCALAR;
 }
 
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return distill_fail(BVD_ERR_HIP, "%s: HIP launch failed: %s", what, hipGetErrorString(e));
-  return BVD_OK;
-}
-
 template <int KIND>
 void launch_dist(int mode, const DistArgs& a, int n, hipStream_t stream) {
   if (mode == MODE_VEC) hipLaunchKernelGGL((distill_dist_kernel<KIND, MODE_VEC>), dim3(n), dim3(kThreads), 0, stream, a);
@@ -369,13 +345,13 @@ void launch_dist(int mode, const DistArgs& a, int n, hipStream_t stream) {
 extern "C" int bv_distill_dist(int kind, const float* student, const float* teacher, float* per_row, double* loss_sum,
                                float* dstudent, int accumulate, int n, int C, int n_global, float t, float ls,
                                float eps, int k, void* stream) {
-  BVD_REQUIRE(n > 0 && C > 0 && n_global >= n, "bv_distill_dist: bad shape n=%d C=%d n_global=%d", n, C, n_global);
-  BVD_REQUIRE(kind >= 0 && kind < BVD_KIND_COUNT, "bv_distill_dist: unknown kind %d", kind);
-  BVD_REQUIRE(student && teacher, "bv_distill_dist: NULL student or teacher");
-  BVD_REQUIRE(kind != BVD_KIND_KL || t > 0.f, "bv_distill_dist: kl needs a temperature t > 0 (got %g)", (double)t);
-  BVD_REQUIRE(kind != BVD_KIND_HARD || C > 1 || ls == 0.f, "bv_distill_dist: label smoothing needs C > 1 (ls / (C - 1))");
-  BVD_REQUIRE(kind != BVD_KIND_AGREE || (k >= 1 && !dstudent), "bv_distill_dist: agree needs k >= 1 and has no derivative");
-  BVD_REQUIRE(eps >= 0.f, "bv_distill_dist: eps < 0");
+  BV_REQUIRE(n > 0 && C > 0 && n_global >= n, "bv_distill_dist: bad shape n=%d C=%d n_global=%d", n, C, n_global);
+  BV_REQUIRE(kind >= 0 && kind < BVD_KIND_COUNT, "bv_distill_dist: unknown kind %d", kind);
+  BV_REQUIRE(student && teacher, "bv_distill_dist: NULL student or teacher");
+  BV_REQUIRE(kind != BVD_KIND_KL || t > 0.f, "bv_distill_dist: kl needs a temperature t > 0 (got %g)", (double)t);
+  BV_REQUIRE(kind != BVD_KIND_HARD || C > 1 || ls == 0.f, "bv_distill_dist: label smoothing needs C > 1 (ls / (C - 1))");
+  BV_REQUIRE(kind != BVD_KIND_AGREE || (k >= 1 && !dstudent), "bv_distill_dist: agree needs k >= 1 and has no derivative");
+  BV_REQUIRE(eps >= 0.f, "bv_distill_dist: eps < 0");
   DistArgs a{student, teacher, per_row, loss_sum, dstudent, accumulate != 0, C, k, n_global, 1.f / (float)n_global, t, ls, eps};
   const int mode = row_mode(C, student, teacher, dstudent);
   hipStream_t s = (hipStream_t)stream;
@@ -387,29 +363,29 @@ extern "C" int bv_distill_dist(int kind, const float* student, const float* teac
     case BVD_KIND_LOGSOFTMAX_EUCLIDEAN: launch_dist<BVD_KIND_LOGSOFTMAX_EUCLIDEAN>(mode, a, n, s); break;
     default: launch_dist<BVD_KIND_AGREE>(mode, a, n, s); break;
   }
-  return check_launch("bv_distill_dist");
+  return bv_check_launch("bv_distill_dist");
 }
 
 extern "C" int bv_distill_entropy(const float* logits, float* per_row, double* sum, int n, int C, int n_global,
                                   void* stream) {
-  BVD_REQUIRE(n > 0 && C > 0 && n_global >= n, "bv_distill_entropy: bad shape n=%d C=%d n_global=%d", n, C, n_global);
-  BVD_REQUIRE(logits, "bv_distill_entropy: NULL logits");
+  BV_REQUIRE(n > 0 && C > 0 && n_global >= n, "bv_distill_entropy: bad shape n=%d C=%d n_global=%d", n, C, n_global);
+  BV_REQUIRE(logits, "bv_distill_entropy: NULL logits");
   const int mode = row_mode(C, logits, nullptr, nullptr);
   hipStream_t s = (hipStream_t)stream;
   if (mode == MODE_VEC) hipLaunchKernelGGL(distill_entropy_kernel<MODE_VEC>, dim3(n), dim3(kThreads), 0, s, logits, per_row, sum, C, n_global);
   else if (mode == MODE_SCALAR) hipLaunchKernelGGL(distill_entropy_kernel<MODE_SCALAR>, dim3(n), dim3(kThreads), 0, s, logits, per_row, sum, C, n_global);
   else hipLaunchKernelGGL(distill_entropy_kernel<MODE_STREAM>, dim3(n), dim3(kThreads), 0, s, logits, per_row, sum, C, n_global);
-  return check_launch("bv_distill_entropy");
+  return bv_check_launch("bv_distill_entropy");
 }
 
 extern "C" int bv_distill_softmax_acc(const float* logits, float* probs, float weight, int accumulate, int n, int C,
                                       void* stream) {
-  BVD_REQUIRE(n > 0 && C > 0, "bv_distill_softmax_acc: bad shape n=%d C=%d", n, C);
-  BVD_REQUIRE(logits && probs, "bv_distill_softmax_acc: NULL logits or probs");
+  BV_REQUIRE(n > 0 && C > 0, "bv_distill_softmax_acc: bad shape n=%d C=%d", n, C);
+  BV_REQUIRE(logits && probs, "bv_distill_softmax_acc: NULL logits or probs");
   const int mode = row_mode(C, logits, probs, nullptr);
   hipStream_t s = (hipStream_t)stream;
   if (mode == MODE_VEC) hipLaunchKernelGGL(distill_softmax_acc_kernel<MODE_VEC>, dim3(n), dim3(kThreads), 0, s, logits, probs, weight, accumulate != 0, C);
   else if (mode == MODE_SCALAR) hipLaunchKernelGGL(distill_softmax_acc_kernel<MODE_SCALAR>, dim3(n), dim3(kThreads), 0, s, logits, probs, weight, accumulate != 0, C);
   else hipLaunchKernelGGL(distill_softmax_acc_kernel<MODE_STREAM>, dim3(n), dim3(kThreads), 0, s, logits, probs, weight, accumulate != 0, C);
-  return check_launch("bv_distill_softmax_acc");
+  return bv_check_launch("bv_distill_softmax_acc");
 }

@@ -20,29 +20,12 @@
 // over the rows; every workgroup sums its rows' three contributions in fp64 registers and issues three atomic adds.
 #include <float.h>
 #include <limits.h>
-#include <stdarg.h>
-#include <stdio.h>
 
+#define BV_STATUS_LINKAGE static   // the whole library is this file
 #include "bv_common.h"
 #include "../../include/bveval.h"
 
-static thread_local char g_err[512] = "";
-
-static int eval_fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define BVE_REQUIRE(cond, ...) \
-  do {                         \
-    if (!(cond)) return eval_fail(BVE_ERR_INVALID_ARG, __VA_ARGS__); \
-  } while (0)
-
-extern "C" const char* bv_eval_last_error(void) { return g_err; }
-extern "C" int bv_eval_version(void) { return BVEVAL_VERSION; }
+BV_DEFINE_STATUS(bv_eval_last_error, bv_eval_version, BVEVAL_VERSION)
 
 namespace {
 
@@ -221,16 +204,14 @@ void launch(bool vec, bool wg, const EvalArgs& a, hipStream_t s) {
 
 extern "C" int bv_eval_classify(int loss_kind, const float* logits, const float* labels, const float* mask, double* acc,
                                 float* row_loss, int* row_top1, int n, int C, void* stream) {
-  BVE_REQUIRE(n > 0 && C > 0, "bv_eval_classify: bad shape n=%d C=%d", n, C);
-  BVE_REQUIRE(loss_kind >= 0 && loss_kind < BVE_LOSS_COUNT, "bv_eval_classify: unknown loss kind %d", loss_kind);
-  BVE_REQUIRE(logits && labels, "bv_eval_classify: NULL logits or labels");
-  BVE_REQUIRE(acc || row_loss || row_top1, "bv_eval_classify: acc, row_loss and row_top1 are all NULL (nothing to compute)");
+  BV_REQUIRE(n > 0 && C > 0, "bv_eval_classify: bad shape n=%d C=%d", n, C);
+  BV_REQUIRE(loss_kind >= 0 && loss_kind < BVE_LOSS_COUNT, "bv_eval_classify: unknown loss kind %d", loss_kind);
+  BV_REQUIRE(logits && labels, "bv_eval_classify: NULL logits or labels");
+  BV_REQUIRE(acc || row_loss || row_top1, "bv_eval_classify: acc, row_loss and row_top1 are all NULL (nothing to compute)");
   const EvalArgs a{logits, labels, mask, acc, row_loss, row_top1, n, C};
   const bool vec = C % 4 == 0 && aligned16(logits) && aligned16(labels);
   const bool wg = C > BVE_WAVE_ROW_MAX_C;
   if (loss_kind == BVE_LOSS_SOFTMAX_XENT) launch<BVE_LOSS_SOFTMAX_XENT>(vec, wg, a, (hipStream_t)stream);
   else launch<BVE_LOSS_SIGMOID_XENT>(vec, wg, a, (hipStream_t)stream);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return eval_fail(BVE_ERR_HIP, "bv_eval_classify: HIP launch failed: %s", hipGetErrorString(e));
-  return BVE_OK;
+  return bv_check_launch("bv_eval_classify");
 }

@@ -6,15 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // ------------------------------------------------------------- siglip loss --
 // trainers/proj/image_text/siglip.py:291-306.  raw[n][B] -> G in place.
 __global__ __launch_bounds__(256) void siglip_loss_kernel(float* __restrict__ raw,

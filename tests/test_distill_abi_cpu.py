@@ -1,7 +1,6 @@
-"""libbvdistill.so on a CPU-only host: it loads, exports exactly what include/bvdistill.h declares, `_lib` binds it
-next to libbvhip.so and routes calls by table, every entry point has a footprint row and every kernel instantiation a
-named parity test, the kernels use no scratch memory, and libbvhip.so's own table is what it was."""
-import ctypes
+"""What is particular to libbvdistill.so on a CPU-only host (what every library must satisfy is in test_libs_cpu.py):
+its four entry points and distance kinds, the exact error strings `_lib.call` reports for it, a footprint row for
+every entry point and a named parity test for every kernel instantiation, and kernels that use no scratch memory."""
 import os
 import re
 import shutil
@@ -10,31 +9,20 @@ import sys
 
 import pytest
 
+from test_libs_cpu import Observer, libs  # noqa: F401  (libs: the fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "bvdistill.h")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def _symbols(header, prefix):
-  src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-  return sorted(set(re.findall(r"^(?:int|long|void|bv_ctx\*|const char\*)\s+(" + prefix + r"\w+)\s*\(", src, re.M)))
-
-
-@pytest.fixture(scope="module")
-def libs():
-  from big_vision_amd import build, _lib
-  build.build(verbose=False)          # hipcc cross-compiles gfx950 without a GPU
-  _lib.load()
-  return _lib
-
-
 def test_header_equals_the_prototype_table_and_the_exports(libs):
-  syms = _symbols(HEADER, "bv_distill_")
-  assert sorted(list(libs.PROTOTYPES_DISTILL) + ["bv_distill_last_error"]) == syms
-  raw = ctypes.CDLL(libs.LIB_DISTILL_PATH)
-  for s in syms:
-    assert hasattr(raw, s), f"libbvdistill.so does not export {s} (declared in include/bvdistill.h)"
-  assert libs.load_distill().bv_distill_version() == 1
+  d = libs.LIBRARIES["distill"]
+  assert d.prototypes is libs.PROTOTYPES_DISTILL and len(d.prototypes) == 4 and os.path.samefile(d.header, HEADER)
+  assert libs.handle("distill").bv_distill_version() == 1
+  from big_vision_amd import build
+  assert build.lib("distill").sources == ["distill.hip"]
+  assert not [r.key for r in build.LIBS if r.key != "distill" and "distill.hip" in r.sources]
   hdr = open(HEADER).read()
   kinds = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define BVD_KIND_(\w+)\s+(\d+)", hdr) if m.group(1) != "COUNT"}
   assert kinds == libs.DISTILL_KINDS
@@ -42,33 +30,14 @@ def test_header_equals_the_prototype_table_and_the_exports(libs):
     assert cite in hdr, cite
 
 
-def test_the_two_libraries_share_no_entry_point_and_libbvhip_is_unchanged(libs):
-  assert not set(libs.PROTOTYPES) & set(libs.PROTOTYPES_DISTILL)
-  first = _symbols(os.path.join(ROOT, "include", "bvhip.h"), "bv_")
-  assert len(first) == len(libs.PROTOTYPES) + 1 == 71            # + bv_last_error; the count before this library existed
-  assert not [s for s in first if s.startswith("bv_distill_")]
-  raw = ctypes.CDLL(libs.LIB_PATH)
-  assert not hasattr(raw, "bv_distill_dist")
-  from big_vision_amd import build
-  assert "distill.hip" not in build.SOURCES and build.DISTILL_SOURCES == ["distill.hip"]
-
-
 def test_call_routes_by_table_and_reports_the_right_librarys_error(libs, monkeypatch):
-  seen = []
-
-  class Obs:
-    def begin(self, name, args):
-      seen.append(name)
-      return name
-
-    def end(self, tok):
-      seen.append("end:" + tok)
-  monkeypatch.setattr(libs, "observer", Obs())
+  obs = Observer()
+  monkeypatch.setattr(libs, "observer", obs)
   with pytest.raises(RuntimeError, match=r"bv_distill_dist failed \(rc=-1\): bv_distill_dist: bad shape"):
     libs.call("bv_distill_dist", 2, None, None, None, None, None, 0, 0, 0, 0, 1.0, 0.0, 0.0, 1, None)
   with pytest.raises(RuntimeError, match=r"bv_distill_entropy failed \(rc=-1\): bv_distill_entropy: NULL logits"):
     libs.call("bv_distill_entropy", None, None, None, 1, 1, 1, None)
-  assert seen == ["bv_distill_dist", "end:bv_distill_dist", "bv_distill_entropy", "end:bv_distill_entropy"]
+  assert obs == ["bv_distill_dist", "end:bv_distill_dist", "bv_distill_entropy", "end:bv_distill_entropy"]
 
 
 def test_every_entry_point_has_a_footprint_row(libs):
@@ -88,7 +57,7 @@ def test_kernel_set_equals_the_list_of_covering_tests(libs):
   sys.path.insert(0, os.path.join(ROOT, "tools"))
   import kernel_inventory as KI
   import test_distill_kernels_gpu as T
-  have = set(KI.inventory(lib=libs.LIB_DISTILL_PATH))
+  have = set(KI.inventory(lib=libs.LIBRARIES["distill"].path))
   assert have == set(T.KERNELS), (sorted(have - set(T.KERNELS)), sorted(set(T.KERNELS) - have))
   for name, test in T.KERNELS.items():
     assert hasattr(T, test.split("[")[0]), (name, test)

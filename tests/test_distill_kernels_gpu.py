@@ -246,7 +246,7 @@ def test_invalid_arguments(dev):
     ops.distill_dist("kl", s, T, per_row=True, n_global=1)
   with pytest.raises(AssertionError, match="Unknown kind of distance"):
     ops.distill_dist("cosine", s, T)
-  lib = _lib.load_distill()
+  lib = _lib.handle("distill")
   assert lib.bv_distill_dist(9, s.data_ptr(), T.data_ptr(), None, None, None, 0, 2, 8, 2, 1.0, 0.0, 0.0, 1, None) == -1
   assert b"unknown kind" in lib.bv_distill_last_error()
   with pytest.raises(RuntimeError, match="GPU"):

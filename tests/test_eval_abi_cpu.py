@@ -1,8 +1,6 @@
-"""libbveval.so on a CPU-only host: it loads, exports exactly what include/bveval.h declares, `_lib` binds it next to
-the other two libraries and routes calls by table, the entry point has its footprint rows and every kernel
-instantiation a named parity test, the kernels use no scratch memory, and the other two libraries' tables are what
-they were."""
-import ctypes
+"""What is particular to libbveval.so on a CPU-only host (what every library must satisfy is in test_libs_cpu.py):
+its one entry point and two losses, the exact error strings `_lib.call` reports for it, its footprint rows and a named
+parity test for each of its eight kernels, and kernels that use no scratch memory."""
 import os
 import re
 import shutil
@@ -11,79 +9,32 @@ import sys
 
 import pytest
 
+from test_libs_cpu import Observer, libs  # noqa: F401  (libs: the fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "bveval.h")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def _symbols(header, prefix):
-  src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-  return sorted(set(re.findall(r"^(?:int|long|void|bv_ctx\*|const char\*)\s+(" + prefix + r"\w+)\s*\(", src, re.M)))
-
-
-@pytest.fixture(scope="module")
-def libs():
-  from big_vision_amd import build, _lib
-  build.build(verbose=False)          # hipcc cross-compiles gfx950 without a GPU
-  _lib.load()
-  return _lib
-
-
 def test_header_equals_the_prototype_table_and_the_exports(libs):
-  syms = _symbols(HEADER, "bv_eval_")
-  assert sorted(list(libs.PROTOTYPES_EVAL) + ["bv_eval_last_error"]) == syms
-  raw = ctypes.CDLL(libs.LIB_EVAL_PATH)
-  for s in syms:
-    assert hasattr(raw, s), f"libbveval.so does not export {s} (declared in include/bveval.h)"
-  exported = subprocess.run(["nm", "-D", "--defined-only", libs.LIB_EVAL_PATH], stdout=subprocess.PIPE, text=True,
-                            check=True).stdout if shutil.which("nm") else ""
-  if exported:      # nothing else of the bv_ namespace leaves the library
-    assert sorted(set(re.findall(r"\b(bv_\w+)$", exported, re.M))) == syms
-  assert libs.load_eval().bv_eval_version() == 1
+  d = libs.LIBRARIES["eval"]
+  assert d.prototypes is libs.PROTOTYPES_EVAL and len(d.prototypes) == 2 and os.path.samefile(d.header, HEADER)
+  assert libs.handle("eval").bv_eval_version() == 1
+  from big_vision_amd import build
+  assert build.lib("eval").sources == ["eval.hip"] and build.LIBS[-1].key == "eval"
+  assert not [r.key for r in build.LIBS if r.key != "eval" and "eval.hip" in r.sources]
   hdr = open(HEADER).read()
-  assert int(re.search(r"#define BVEVAL_VERSION\s+(\d+)", hdr).group(1)) == 1
   losses = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define BVE_LOSS_(\w+)\s+(\d+)", hdr) if m.group(1) != "COUNT"}
   assert losses == libs.EVAL_LOSSES == {"softmax_xent": 0, "sigmoid_xent": 1}
-  codes = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define BVE_(OK|ERR_\w+)\s+\(?(-?\d+)\)?", hdr)}
-  first = open(os.path.join(ROOT, "include", "bvhip.h")).read()
-  for name, value in codes.items():     # the values of bvhip.h
-    assert int(re.search(r"#define BV_" + name + r"\s+\(?(-?\d+)\)?", first).group(1)) == value, name
-  assert set(codes) == {"OK", "ERR_INVALID_ARG", "ERR_UNSUPPORTED", "ERR_HIP"}
   for cite in ("evaluators/classification.py:", "utils.py:"):
     assert cite in hdr, cite
   import _eval_bounds as B
   assert int(re.search(r"#define BVE_WAVE_ROW_MAX_C\s+(\d+)", hdr).group(1)) == B.WAVE_ROW_MAX_C
 
 
-def test_the_three_libraries_share_no_entry_point_and_the_others_are_unchanged(libs):
-  tables = (libs.PROTOTYPES, libs.PROTOTYPES_DISTILL, libs.PROTOTYPES_EVAL)
-  for i, a in enumerate(tables):
-    for b in tables[i + 1:]:
-      assert not set(a) & set(b)
-  first = _symbols(os.path.join(ROOT, "include", "bvhip.h"), "bv_")
-  assert len(first) == len(libs.PROTOTYPES) + 1 == 71
-  assert not [s for s in first if s.startswith("bv_eval_")]
-  assert len(libs.PROTOTYPES_DISTILL) == 4
-  for path in (libs.LIB_PATH, libs.LIB_DISTILL_PATH):
-    assert not hasattr(ctypes.CDLL(path), "bv_eval_classify"), path
-  from big_vision_amd import build
-  assert build.EVAL_SOURCES == ["eval.hip"]
-  assert "eval.hip" not in build.SOURCES and "eval.hip" not in build.DISTILL_SOURCES
-  assert build.LIBS[-1] == (build.LIB_EVAL, build.EVAL_SOURCES) and len(build.LIBS) == 3
-  assert os.path.samefile(build.LIB_EVAL, libs.LIB_EVAL_PATH)
-
-
 def test_call_routes_by_table_and_reports_the_right_librarys_error(libs, monkeypatch):
-  seen = []
-
-  class Obs:
-    def begin(self, name, args):
-      seen.append(name)
-      return name
-
-    def end(self, tok):
-      seen.append("end:" + tok)
-  monkeypatch.setattr(libs, "observer", Obs())
+  obs = Observer()
+  monkeypatch.setattr(libs, "observer", obs)
   with pytest.raises(RuntimeError, match=r"bv_eval_classify failed \(rc=-1\): bv_eval_classify: bad shape n=0 C=5"):
     libs.call("bv_eval_classify", 0, None, None, None, None, None, None, 0, 5, None)
   with pytest.raises(RuntimeError, match=r"bv_eval_classify failed \(rc=-1\): bv_eval_classify: unknown loss kind 7"):
@@ -93,8 +44,8 @@ def test_call_routes_by_table_and_reports_the_right_librarys_error(libs, monkeyp
   # the other libraries still answer with their own strings
   with pytest.raises(RuntimeError, match=r"bv_distill_entropy failed \(rc=-1\): bv_distill_entropy: NULL logits"):
     libs.call("bv_distill_entropy", None, None, None, 1, 1, 1, None)
-  assert seen == ["bv_eval_classify", "end:bv_eval_classify"] * 3 + ["bv_distill_entropy", "end:bv_distill_entropy"]
-  assert libs.load_eval().bv_eval_last_error() == b"bv_eval_classify: NULL logits or labels"
+  assert obs == ["bv_eval_classify", "end:bv_eval_classify"] * 3 + ["bv_distill_entropy", "end:bv_distill_entropy"]
+  assert libs.handle("eval").bv_eval_last_error() == b"bv_eval_classify: NULL logits or labels"
 
 
 def test_ops_wrapper_refuses_cpu_tensors_and_unknown_losses(libs):
@@ -123,7 +74,7 @@ def test_kernel_set_equals_the_list_of_covering_tests(libs):
   sys.path.insert(0, os.path.join(ROOT, "tools"))
   import kernel_inventory as KI
   import test_eval_kernels_gpu as T
-  have = set(KI.inventory(lib=libs.LIB_EVAL_PATH))
+  have = set(KI.inventory(lib=libs.LIBRARIES["eval"].path))
   assert have == set(T.KERNELS), (sorted(have - set(T.KERNELS)), sorted(set(T.KERNELS) - have))
   assert len(have) == 8                       # 2 losses x 2 load widths x 2 row mappings
   for name, test in T.KERNELS.items():

@@ -193,7 +193,7 @@ def test_every_optional_pointer_null_in_turn(dev):
         if acc is not None:
           assert acc[0].item() == full[0][0].item() and acc[2].item() == full[0][2].item()
           assert abs(acc[1].item() - full[0][1].item()) <= 1e-12 * abs(full[0][1].item())
-  lib = _lib.load_eval()
+  lib = _lib.handle("eval")
   assert lib.bv_eval_classify(0, p(xd), p(yd), p(md), None, None, None, n, C, None) == -1     # BVE_ERR_INVALID_ARG
   assert b"bv_eval_classify" in lib.bv_eval_last_error() and b"all NULL" in lib.bv_eval_last_error()
 
@@ -228,7 +228,7 @@ def test_views_off_the_16_byte_grid_take_the_4_byte_path(dev, C):
 def test_invalid_arguments(dev):
   """Every BVE_ERR_INVALID_ARG of include/bveval.h, with the entry point's name in the message."""
   from big_vision_amd import _lib, ops
-  lib = _lib.load_eval()
+  lib = _lib.handle("eval")
   x = B.dyadic_logits(2, 8, 1).to(dev)
   y = B.onehot_labels(x.cpu(), 2).to(dev)
   acc = torch.zeros(3, device=dev, dtype=F64)

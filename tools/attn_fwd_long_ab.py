@@ -31,7 +31,7 @@ def build():
   B.build(force=False, verbose=False)
   os.makedirs(OUT, exist_ok=True)
   objdir = os.path.join(B.HERE, "build")
-  others = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in B.SOURCES if s != "attention3.hip"]
+  others = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in B.lib("hip").sources if s != "attention3.hip"]
   for v, flags in VARIANTS.items():
     obj = os.path.join(OUT, f"attention3_{v}.o")
     subprocess.check_call(["hipcc", *B.FLAGS, *flags, "-x", "hip", "-c", os.path.join(B.CSRC, "attention3.hip"), "-o", obj])
@@ -41,7 +41,7 @@ def build():
 
 def child(v):
   from big_vision_amd import _lib
-  _lib.LIB_PATH = lib_of(v)
+  _lib.LIBRARIES["hip"].path = lib_of(v)
   import torch
   from big_vision_amd import ops
   dev = torch.device("cuda:0")

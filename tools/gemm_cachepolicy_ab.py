@@ -25,7 +25,7 @@ def build():
   B.build(force=False, verbose=False)       # the product's objects are the other translation units of every variant
   os.makedirs(OUT, exist_ok=True)
   objdir = os.path.join(B.HERE, "build")
-  others = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in B.SOURCES if s != "gemm256.hip"]
+  others = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in B.lib("hip").sources if s != "gemm256.hip"]
   procs = []
   for a, b in VARIANTS:
     obj = os.path.join(OUT, f"gemm256_a{a}_b{b}.o")
@@ -40,7 +40,7 @@ def build():
 
 def child(a, b):
   from big_vision_amd import _lib
-  _lib.LIB_PATH = lib_of(a, b)
+  _lib.LIBRARIES["hip"].path = lib_of(a, b)
   import torch
   from big_vision_amd import ops
   dev = torch.device("cuda:0")

@@ -31,8 +31,8 @@ def main():
   from big_vision_amd import _lib
   if args.lib:
     import ctypes
-    _lib.LIB_PATH = os.path.abspath(args.lib)
-    if not hasattr(ctypes.CDLL(_lib.LIB_PATH), "bv_trace_step"):   # a build from before the trace stage: Adam only
+    _lib.LIBRARIES["hip"].path = os.path.abspath(args.lib)
+    if not hasattr(ctypes.CDLL(_lib.LIBRARIES["hip"].path), "bv_trace_step"):   # a build from before the trace stage: Adam only
       _lib.PROTOTYPES.pop("bv_trace_step")
   from big_vision_amd import ops
   dev = torch.device("cuda:0")

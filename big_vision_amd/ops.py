@@ -768,3 +768,58 @@ def eval_classify(loss_name, logits, labels, mask=None, acc=None, per_row=False)
   _lib.call("bv_eval_classify", _lib.EVAL_LOSSES[loss_name], _p(logits), _p(labels), _p(mask), _p(acc), _p(rows),
             _p(top1), n, C, _stream())
   return (acc, rows, top1) if per_row else acc
+
+
+# ---- the B x B tail of the contrastive evaluator: bv_sgemm_strided + bv_eval_classify, nothing new on the device
+_eye_cache = {}
+
+
+def _eye_block(v, row_offset, B, device):
+  """Rows [row_offset, row_offset + v) of the B x B identity, fp32, cached per (v, row_offset, B) and device: the
+  one-hot labels of v examples whose positives sit on the diagonal.  4 v B bytes; only ever read."""
+  key = (v, row_offset, B, device)
+  eye = _eye_cache.get(key)
+  if eye is None:
+    eye = _eye_cache[key] = torch.zeros((v, B), device=device, dtype=F32)
+    eye[torch.arange(v, device=device), row_offset + torch.arange(v, device=device)] = 1.0
+  return eye
+
+
+def contrastive_eval(zimg, ztxt, t, acc_it, acc_ti, row_offset=0, cols=None, log_t=None, per_row=False):
+  """utils.py:246-273 (`bidirectional_contrastive_loss`, reduction=False) for v real examples, four launches:
+    logits_it [v, B] = t zimg ztxt_all^T     bv_sgemm_strided (fp32)
+    logits_ti [v, B] = t ztxt zimg_all^T     the same entry point with the operands swapped: no transpose
+    acc_it += (hits, sum of row losses, v)   bv_eval_classify("softmax_xent", logits_it, labels = identity block)
+    acc_ti += ...                            the same on logits_ti
+  zimg, ztxt: fp32 [v, E], this caller's examples.  cols = (zimg_all, ztxt_all), fp32 [B, E]: the columns they are
+  ranked against (None: themselves, B = v); example i is column row_offset + i.  acc_it / acc_ti: fp64 [3] on the device,
+  added to.  `hits` of acc_it is the reference's `ncorrect` (argmax over axis 1 only, :272, lowest index wins); the
+  per-example loss is 0.5 (row loss of logits_it + row loss of logits_ti) (:259-261).
+  t: a host number (the GEMM's alpha), or with log_t (a device tensor holding log t, the model's `t/parameter`) the
+  GEMM's device-side `log_alpha`; a device tensor t without log_t is turned into one.  Never read back to the host.
+  v = 0 launches nothing.  per_row=True returns (row_loss_it, row_loss_ti, top1_it) of bv_eval_classify, else None."""
+  _chk(zimg, F32, "contrastive_eval.zimg"); _chk(ztxt, F32, "contrastive_eval.ztxt")
+  v, E = zimg.shape
+  assert ztxt.shape == (v, E) and zimg.is_contiguous() and ztxt.is_contiguous(), "contrastive_eval: zimg / ztxt [v, E]"
+  zimg_all, ztxt_all = (zimg, ztxt) if cols is None else cols
+  _chk(zimg_all, F32, "contrastive_eval.cols[0]"); _chk(ztxt_all, F32, "contrastive_eval.cols[1]")
+  B = zimg_all.shape[0]
+  assert zimg_all.shape == ztxt_all.shape == (B, E) and zimg_all.is_contiguous() and ztxt_all.is_contiguous()
+  if not 0 <= row_offset <= B - v:
+    raise ValueError(f"contrastive_eval: diagonal [{row_offset}, {row_offset + v}) outside B={B}")
+  if v == 0:
+    return (None, None, None) if per_row else None
+  alpha = 1.0
+  if log_t is None and torch.is_tensor(t):
+    log_t = torch.log(t)
+  if log_t is not None:
+    log_t = _chk(log_t, F32, "contrastive_eval.log_t").reshape(-1)[:1]
+  else:
+    alpha = float(t)
+  labels = _eye_block(v, row_offset, B, zimg.device)
+  rows = []
+  for a, b, acc in ((zimg, ztxt_all, acc_it), (ztxt, zimg_all, acc_ti)):
+    logits = torch.empty((v, B), device=zimg.device, dtype=F32)
+    sgemm(a, E, 1, b, 1, E, logits, v, B, E, alpha=alpha, log_alpha=log_t)
+    rows.append(eval_classify("softmax_xent", logits, labels, None, acc=acc, per_row=per_row))
+  return (rows[0][1], rows[1][1], rows[0][2]) if per_row else None

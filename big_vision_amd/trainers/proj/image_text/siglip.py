@@ -278,12 +278,20 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
   return update_fn
 
 
-def make_predict_fn(model):
+def make_predict_fn(model, config=None):
   """`predict_fn(train_state, batch)` handed to the evaluators (siglip.py:388-392): either of
-  batch["image"] / batch["labels"] may be missing."""
+  batch["image"] / batch["labels"] may be missing.  With `config` the forward runs on `config.residual_stream`,
+  like `update_fn` (and like train.make_predict_fn); it reads the parameters and changes nothing."""
+  stream = config.get("residual_stream", "float32") if config is not None else None
+
   def predict_fn(train_state, batch):
-    zimg, ztxt, out = model.apply({"params": train_state["params"]}, batch.get("image", None),
-                                  batch.get("labels", None), collect=False)
+    old = E.set_residual_stream(stream) if stream is not None else None
+    try:
+      zimg, ztxt, out = model.apply({"params": train_state["params"]}, batch.get("image", None),
+                                    batch.get("labels", None), collect=False)
+    finally:
+      if stream is not None:
+        E.set_residual_stream(old)
     return zimg, ztxt, out
   return predict_fn
 

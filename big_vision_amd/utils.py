@@ -1,6 +1,7 @@
 """Host-side utilities: the subset of big_vision/utils.py (Copyright 2024 Big Vision Authors, Apache-2.0) that
 the hot path's callers use - leaf naming (utils.py:616-862), regex masks (:1169-1212), durations -> steps
-(:1002-1067), learning-rate schedules (:1070-1143), .npz parameter loading (:133-227), mixup (:1146-1154).
+(:1002-1067), learning-rate schedules (:1070-1143), .npz parameter loading (:133-227), mixup (:1146-1154), and the
+host side of `bidirectional_contrastive_loss` (:246-273; its arithmetic is ops.contrastive_eval).
 
 What is contract here is BEHAVIOUR: configs, checkpoints and schedules written for the reference must mean the
 same thing, and the reference's own known-answer tests (utils_test.py:144-281) are restated in
@@ -311,3 +312,49 @@ def get_mixup(rng, p, step=0):
 def mixup(rng, *things, p, **more_things):
   """The legacy spelling (utils.py:1158-1159)."""
   return get_mixup(rng, p)(*things, **more_things)
+
+
+# ------------------------------------------------- contrastive evaluation ----
+def host_mask(mask):
+  """`_mask` [b] as a bool tensor on the host (it decides the shapes of the launches); a device tensor is copied."""
+  import torch
+  return torch.as_tensor(mask).cpu().reshape(-1) != 0
+
+
+def real_rows(z, mask):
+  """The rows of z [b, ...] where the host bool `mask` [b] is set: z itself when all are, else an index select."""
+  import torch
+  if bool(mask.all()):
+    return z
+  return z.index_select(0, torch.nonzero(mask).reshape(-1).to(z.device))
+
+
+def bidirectional_contrastive_loss(zimg, ztxt, t, mask=None, reduction=False):
+  """Mirror of utils.bidirectional_contrastive_loss (utils.py:246-273) on ops.contrastive_eval, the launch sequence of
+  evaluators/proj/image_text/contrastive.py: returns (l, {"ncorrect": ...}).  zimg, ztxt: fp32 [b, E] on the GPU; t: a
+  number or a device tensor; mask: [b] on the host (None = all real).  Padded examples are removed before the launches,
+  which equals the reference's -inf masking of rows and columns (:254-256; see the evaluator's docstring).
+  reduction=False: l is [b], 0.5 (l1 + l2) per example and 0 where masked (:259-264), ncorrect is bool [b], the
+  image -> text argmax equal to the own index (:272).  l is fp64: the exact half-sum of the kernel's two fp32 row
+  losses, so that its sum IS what the evaluator accumulates.  A padded example at index 0 reads ncorrect = True, as in
+  the reference (the argmax of a row of -inf is 0); like there, every consumer multiplies by the mask.
+  reduction=True: device scalars: the means, or with a mask sum(x mask) / (sum(mask) + 1e-8) (:266-268)."""
+  import torch
+  from big_vision_amd import ops
+  b = zimg.shape[0]
+  real = torch.ones(b, dtype=torch.bool) if mask is None else host_mask(mask)
+  zi, zt = (real_rows(z.to(torch.float32).contiguous(), real) for z in (zimg, ztxt))
+  acc = torch.zeros((2, 3), device=zimg.device, dtype=torch.float64)
+  row_it, row_ti, top1 = ops.contrastive_eval(zi, zt, t, acc[0], acc[1], per_row=True)
+  if reduction:
+    n = float(b) if mask is None else float(real.sum()) + 1e-8
+    return 0.5 * (acc[0, 1] + acc[1, 1]) / n, {"ncorrect": acc[0, 0] / n}
+  l = torch.zeros(b, device=zimg.device, dtype=torch.float64)
+  ncorrect = torch.zeros(b, device=zimg.device, dtype=torch.bool)
+  if b and not bool(real[0]):
+    ncorrect[0] = True
+  if row_it is not None:
+    idx = torch.nonzero(real).reshape(-1).to(zimg.device)
+    l[idx] = 0.5 * (row_it.double() + row_ti.double())
+    ncorrect[idx] = top1.long() == torch.arange(idx.numel(), device=zimg.device)
+  return l, {"ncorrect": ncorrect}

@@ -139,8 +139,10 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
     # nothing until the loss, two_towers.py:56-75; same kernels on the same inputs, identical results).
     # config.tower_streams = 1 puts both towers back on the caller's stream.
     ex.streams = int(config.get("tower_streams", 2) or 1)
-    img_frozen = all(e in store.frozen for e in store.entries if e.startswith("img/"))
-    txt_frozen = all(e in store.frozen for e in store.entries if e.startswith("txt/"))
+    # (a model without a `txt/` subtree - one_tower: both inputs go through `img/` - has no frozen text tower)
+    owned = lambda p: [e for e in store.entries if e.startswith(p)]
+    img_frozen = bool(owned("img/")) and all(e in store.frozen for e in owned("img/"))
+    txt_frozen = bool(owned("txt/")) and all(e in store.frozen for e in owned("txt/"))
     t_param = store.t("t")
     b_param = store.t("b") if "b" in store.entries else None
     # N > 1: the gradient all-reduce overlaps the (last) backward, see dp.GradSync

@@ -3,16 +3,40 @@ import json
 
 
 class FieldReference:
-  """Tiny stand-in: holds a value; `.get()` returns it."""
+  """Lazy stand-in: holds a value or another reference; `.get()` resolves it.  Arithmetic on a reference gives a
+  derived reference that follows its operands (`config.get_ref("lr") * 0.5`), as configs use it to tie fields."""
 
-  def __init__(self, default, field_type=None):
+  def __init__(self, default, field_type=None, op=None):
     self._value = default
+    self._op = op          # None, or (fn, other): get() = fn(value, other), both resolved
 
   def get(self):
-    return self._value
+    v = self._value.get() if isinstance(self._value, FieldReference) else self._value
+    if self._op is not None:
+      fn, other = self._op
+      v = fn(v, other.get() if isinstance(other, FieldReference) else other)
+    return v
 
   def set(self, v):
-    self._value = v
+    self._value, self._op = v, None
+
+  def _derive(self, fn, other):
+    return FieldReference(self, op=(fn, other))
+
+  def __add__(self, o): return self._derive(lambda a, b: a + b, o)
+  def __radd__(self, o): return self._derive(lambda a, b: b + a, o)
+  def __sub__(self, o): return self._derive(lambda a, b: a - b, o)
+  def __rsub__(self, o): return self._derive(lambda a, b: b - a, o)
+  def __mul__(self, o): return self._derive(lambda a, b: a * b, o)
+  def __rmul__(self, o): return self._derive(lambda a, b: b * a, o)
+  def __truediv__(self, o): return self._derive(lambda a, b: a / b, o)
+  def __rtruediv__(self, o): return self._derive(lambda a, b: b / a, o)
+  def __floordiv__(self, o): return self._derive(lambda a, b: a // b, o)
+  def __neg__(self): return self._derive(lambda a, _: -a, None)
+
+
+def _res(v):
+  return v.get() if isinstance(v, FieldReference) else v
 
 
 class ConfigDict:
@@ -28,7 +52,7 @@ class ConfigDict:
   # -- mapping protocol
   def _wrap(self, v):
     if isinstance(v, FieldReference):
-      v = v.get()
+      return v               # stays a reference: the field follows its source
     if isinstance(v, dict) and self._convert_dict:
       return ConfigDict(v)
     return v
@@ -36,7 +60,11 @@ class ConfigDict:
   def __setitem__(self, key, value):
     if self._locked and key not in self._fields:
       raise KeyError(f"Key '{key}' does not exist and the ConfigDict is locked")
-    self._fields[key] = self._wrap(value)
+    old = self._fields.get(key)
+    if isinstance(old, FieldReference) and not isinstance(value, FieldReference):
+      old.set(self._wrap(value))      # every reference taken with get_ref(key) sees the new value
+    else:
+      self._fields[key] = self._wrap(value)
 
   def __getitem__(self, key):
     if "." in key and key not in self._fields:
@@ -44,7 +72,7 @@ class ConfigDict:
       for part in key.split("."):
         node = node[part]
       return node
-    return self._fields[key]
+    return _res(self._fields[key])
 
   def __delitem__(self, key):
     del self._fields[key]
@@ -56,7 +84,7 @@ class ConfigDict:
     if key.startswith("__"):
       raise AttributeError(key)
     try:
-      return self._fields[key]
+      return _res(self._fields[key])
     except KeyError as e:
       raise AttributeError(f"'ConfigDict' has no attribute '{key}'") from e
 
@@ -76,22 +104,25 @@ class ConfigDict:
     return self._fields.keys()
 
   def values(self):
-    return self._fields.values()
+    return [_res(v) for v in self._fields.values()]
 
   def items(self):
-    return self._fields.items()
+    return [(k, _res(v)) for k, v in self._fields.items()]
 
   def get(self, key, default=None):
-    return self._fields.get(key, default)
+    return _res(self._fields.get(key, default))
 
   def get_ref(self, key):
-    return FieldReference(self._fields[key])
+    """The field as a reference; the field itself becomes one, so a later assignment to it reaches every holder."""
+    if not isinstance(self._fields[key], FieldReference):
+      self._fields[key] = FieldReference(self._fields[key])
+    return self._fields[key]
 
   def update(self, *other, **kwargs):
     for o in other:
       for k, v in (o.items() if hasattr(o, "items") else o):
-        if k in self._fields and isinstance(self._fields[k], ConfigDict) and hasattr(v, "items"):
-          self._fields[k].update(v)
+        if k in self._fields and isinstance(_res(self._fields[k]), ConfigDict) and hasattr(v, "items"):
+          _res(self._fields[k]).update(v)
         else:
           self[k] = v
     for k, v in kwargs.items():
@@ -100,18 +131,18 @@ class ConfigDict:
   def setdefault(self, key, default=None):
     if key not in self._fields:
       self[key] = default
-    return self._fields[key]
+    return _res(self._fields[key])
 
   def lock(self):
     object.__setattr__(self, "_locked", True)
-    for v in self._fields.values():
+    for v in self.values():
       if isinstance(v, ConfigDict):
         v.lock()
     return self
 
   def unlock(self):
     object.__setattr__(self, "_locked", False)
-    for v in self._fields.values():
+    for v in self.values():
       if isinstance(v, ConfigDict):
         v.unlock()
     return self
@@ -133,7 +164,7 @@ class ConfigDict:
     return self._locked
 
   def to_dict(self):
-    return {k: (v.to_dict() if isinstance(v, ConfigDict) else v) for k, v in self._fields.items()}
+    return {k: (v.to_dict() if isinstance(v, ConfigDict) else v) for k, v in self.items()}
 
   def to_json(self, **kw):
     return json.dumps(self.to_dict(), default=str, **kw)

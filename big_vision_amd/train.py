@@ -51,8 +51,9 @@ def _loss_kernel(config):
   return LOSSES[name]
 
 
-def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_steps=None, device=None):
-  """Parameter store + optimizer laid out for `config` (replaces train.py:191-262)."""
+def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_steps=None, device=None, after_init=None):
+  """Parameter store + optimizer laid out for `config` (replaces train.py:191-262).  after_init(store): edits of the
+  random init that a checkpoint load may still overwrite (a trainer's `init_head_bias`)."""
   from big_vision_amd.models.vit import _seed_of
   comm = comm or dp.Comm()
   device = device or torch.device("cuda", torch.cuda.current_device())
@@ -71,6 +72,9 @@ def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_step
       frozen.add(e.name)
   store = ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
   store.init_random(_seed_of(rng))
+  if after_init is not None:
+    after_init(store)
+    store.mark_dirty()
   if config.get("model_init"):
     _load_model_init(model, config, store)
   store.refresh_shadow()
@@ -121,35 +125,65 @@ def loss_fn(model, params, images, labels, config, comm=None):
   return acc[0]
 
 
+def mixup_p(config):
+  """`config.mixup.p` (train.py:281), 0.0 without a mixup section."""
+  return float(config.get("mixup", {}).get("p", 0.0) or 0.0) if config.get("mixup") else 0.0
+
+
+def prepare_batch(batch, rng, opt, mix_p):
+  """fp32 contiguous (images, labels) of `batch`, mixed up when `mix_p` (train.py:283-289): one coefficient per step
+  (fold_in(rng, step), or the batch's own `mixup_a`), the roll is per device."""
+  images = batch["image"].to(F32).contiguous()
+  labels = batch["labels"].to(F32).contiguous()
+  if mix_p:
+    a = batch.get("mixup_a") if isinstance(batch, dict) else None
+    if a is None:
+      a = u.get_mixup_coefficient(rng, bv_optax.get_count(opt), mix_p)
+    images, labels = ops.mixup(images, a), ops.mixup(labels, a)
+  return images, labels
+
+
+def step_dropout(model, rng, opt, comm):
+  """Dropout (vit.py:228,100,109,76; train.py:298 rngs={"dropout": rng_model}): one key per step and rank; None for a
+  model without dropout."""
+  if float(getattr(model, "dropout", 0.0) or 0.0) <= 0.0:
+    return None
+  if rng is None:
+    raise ValueError("the model has dropout > 0: update_fn needs an rng")
+  from big_vision_amd.models.vit import _seed_of
+  return E.Dropout(model.dropout, _seed_of(rng)).fold("step", int(bv_optax.get_count(opt)), "rank", int(comm.rank))
+
+
+def in_residual_stream(config, fn):
+  """`fn` run on config.residual_stream ("float32" = the reference's arithmetic, "bfloat16"): set for the duration of
+  each call and restored afterwards, so model.apply / other trainers in the process keep their own."""
+  stream = config.get("residual_stream", "float32")
+
+  def wrapped(*args, **kw):
+    old = E.set_residual_stream(stream)
+    try:
+      return fn(*args, **kw)
+    finally:
+      E.set_residual_stream(old)
+  return wrapped
+
+
 def make_update_fn(model, config, comm=None):
   """Builds `update_fn(train_state, rng, batch)` (train.py:275-315)."""
   comm = comm or dp.Comm()
   loss_kernel = _loss_kernel(config)
-  mix_p = float(config.get("mixup", {}).get("p", 0.0) or 0.0) if config.get("mixup") else 0.0
+  mix_p = mixup_p(config)
 
   def update_fn(train_state, rng, batch):
-    images, labels = batch["image"], batch["labels"]
     params, opt = train_state["params"], train_state["opt"]
     store = params.store
     store.want_grads = True
     store.refresh_shadow()   # no-op when clean; picks up load_tree() / in-place master edits
     store.zero_grad()
-    images = images.to(F32).contiguous()
-    labels = labels.to(F32).contiguous()
-    if mix_p:
-      # train.py:283-289: one coefficient per step (fold_in(rng, step)), the roll is per device
-      a = batch.get("mixup_a") if isinstance(batch, dict) else None
-      if a is None:
-        a = u.get_mixup_coefficient(rng, bv_optax.get_count(opt), mix_p)
-      images, labels = ops.mixup(images, a), ops.mixup(labels, a)
+    images, labels = prepare_batch(batch, rng, opt, mix_p)
     n = images.shape[0]
     ex = model.executor(store, "", model.grid(tuple(images.shape)))
-    # dropout (vit.py:228,100,109,76; train.py:298 rngs={"dropout": rng_model}): one key per step and rank
-    drop = None
-    if float(getattr(model, "dropout", 0.0) or 0.0) > 0.0:
-      if rng is None:
-        raise ValueError("the model has dropout > 0: update_fn needs an rng")
-      drop = E.Dropout(model.dropout, _seed_of(rng)).fold("step", int(bv_optax.get_count(opt)), "rank", int(comm.rank))
+    drop = step_dropout(model, rng, opt, comm)
     logits, _, ctx = ex.fwd(images, save=True, drop=drop)
     acc = torch.zeros(1, device=images.device, dtype=torch.float64)
     dlogits = loss_kernel(logits.contiguous(), labels, acc, want_grad=True, n_global=n * comm.size)
@@ -165,18 +199,7 @@ def make_update_fn(model, config, comm=None):
     measurements.update(opt.step())
     return {"params": params, "opt": opt}, measurements
 
-  # config.residual_stream ("float32" = the reference's arithmetic, "bfloat16"): set for the duration of
-  # each step and restored afterwards, so model.apply / other trainers in the process keep their own
-  stream = config.get("residual_stream", "float32")
-  inner = update_fn
-
-  def update_fn(train_state, rng, batch):
-    old = E.set_residual_stream(stream)
-    try:
-      return inner(train_state, rng, batch)
-    finally:
-      E.set_residual_stream(old)
-  return update_fn
+  return in_residual_stream(config, update_fn)
 
 
 def make_predict_fn(model, config=None):

@@ -24,6 +24,7 @@ import threading
 import weakref
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from big_vision_amd import ops
@@ -379,6 +380,27 @@ def linear_bwd_x(dy_bf, w: _W, out_dtype=BF16, **kw):
     dx = ops.gemm(dyp, w.bf_np(), a_kmajor=True, b_kmajor=True, out_dtype=out_dtype, **kw)
     return dx[:, :K].contiguous() if w.kpad else dx
   return ops.gemm(dy_bf, w.bf, a_kmajor=True, b_kmajor=True, out_dtype=out_dtype, **kw)
+
+
+def input_shape(x):
+  """Shape that keys a tower's layout: of the tensor ([n, H, W, 3] pixels, [n, L] tokens), or - NaFlex
+  (models/proj/image_text/naflex_vit.py:227) - of the patches of the (patches, ptype, yabs, xabs) tuple; None for an
+  absent input."""
+  if x is None:
+    return None
+  return tuple(x[0].shape) if isinstance(x, (tuple, list)) else tuple(x.shape)
+
+
+def seed_of(rng) -> int:
+  """The 63-bit integer seed of whatever a caller hands in as `rng` (a torch.Generator, an int, a jax-style key
+  array): parameter init, Dropout keys and the mixup coefficient all start from it."""
+  if isinstance(rng, torch.Generator):
+    return int(rng.initial_seed())
+  a = np.asarray(rng).astype(np.uint64).ravel()
+  s = 0
+  for v in a:
+    s = (s * 1000003 + int(v)) % (2 ** 63)
+  return int(s)
 
 
 class Dropout:

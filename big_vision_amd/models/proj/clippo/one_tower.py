@@ -32,13 +32,9 @@ from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import utils
 from big_vision_amd.models.proj.image_text.two_towers import MODELS_PKG, TwoTowersExec
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store, external_leaf_names, scan_name
+from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store, entry_leaf_names, make_store
 
 F32 = torch.float32
-
-
-def _shape_of(x):
-  return None if x is None else tuple(x.shape)
 
 
 def _split_rows(tree, ni, nt):
@@ -163,26 +159,17 @@ class Model:
   def leaf_names(self, image_shape, text_shape=None):
     """Leaf names as presented (stacked `encoderblock` for a tower built with scan=True)."""
     hw = self.image_tower.grid(self._geometry(image_shape, text_shape))
-    return external_leaf_names([l for e in self.entries("", hw) for l, _ in e.flax_leaves()], self.scan_prefixes())
+    return entry_leaf_names(self.entries("", hw), self.scan_prefixes())
 
   def make_store(self, image_shape, text_shape=None, device=None, frozen_leaves=()):
     """Allocates the flat parameter store of the tower (+ t).  `frozen_leaves`: see two_towers.Model.make_store."""
-    device = device or torch.device("cuda", torch.cuda.current_device())
-    ents = self.entries("", self.image_tower.grid(self._geometry(image_shape, text_shape)))
-    frozen_leaves, sp, frozen = set(frozen_leaves), self.scan_prefixes(), set()
-    for e in ents:
-      hits = [scan_name(leaf, sp)[0] in frozen_leaves for leaf, _ in e.flax_leaves()]
-      if any(hits) and not all(hits):
-        raise NotImplementedError(f"fused tensor {e.name} is only partially frozen")
-      if all(hits):
-        frozen.add(e.name)
-    return ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
+    hw = self.image_tower.grid(self._geometry(image_shape, text_shape))
+    return make_store(self.entries("", hw), device, self.scan_prefixes(), frozen_leaves)
 
   def init(self, rng, image, text=None, **kw):
     del kw
-    from big_vision_amd.models.vit import _seed_of
-    store = self.make_store(_shape_of(image), _shape_of(text))
-    store.init_random(_seed_of(rng))
+    store = self.make_store(E.input_shape(image), E.input_shape(text))
+    store.init_random(E.seed_of(rng))
     store.refresh_shadow()
     return {"params": store.tree()}
 
@@ -200,12 +187,11 @@ class Model:
     if train and float(getattr(self.image_tower, "dropout", 0.0) or 0.0) > 0.0:
       if not rngs or "dropout" not in rngs:
         raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-      from big_vision_amd.models import vit as _vit
-      drop_key = _vit._seed_of(rngs["dropout"])
+      drop_key = E.seed_of(rngs["dropout"])
     if text is not None:
       _require_rendered_text(text)
     params = variables["params"]
-    ishape, tshape = _shape_of(image), _shape_of(text)
+    ishape, tshape = E.input_shape(image), E.input_shape(text)
     if isinstance(params, ParamTree) and params.store is not None:
       store, prefix = params.store, params.prefix
     else:

@@ -255,7 +255,7 @@ class _Model:
     del kw
     dev = text.device if torch.is_tensor(text) and text.is_cuda else torch.device("cuda", torch.cuda.current_device())
     store = ParamStore(self.entries("", text.shape[1]), dev)
-    store.init_random(vit._seed_of(rng))
+    store.init_random(E.seed_of(rng))
     store.refresh_shadow()
     return {"params": store.tree()}
 

@@ -237,7 +237,7 @@ class _Model:
     patches = image[0]
     dev = patches.device if torch.is_tensor(patches) and patches.is_cuda else torch.device("cuda", torch.cuda.current_device())
     store = ParamStore(self.entries("", int(patches.shape[-1])), dev, scan_prefixes=self.scan_prefixes())
-    store.init_random(vit._seed_of(rng))
+    store.init_random(E.seed_of(rng))
     store.refresh_shadow()
     return {"params": store.tree()}
 

@@ -18,7 +18,7 @@ import torch
 from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import utils
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store
+from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store, entry_leaf_names, make_store
 
 F32 = torch.float32
 MODELS_PKG = "big_vision_amd.models"
@@ -266,37 +266,21 @@ class Model:
 
   def leaf_names(self, image_shape, text_shape):
     """Leaf names as presented (stacked `encoderblock` for towers built with scan=True)."""
-    from big_vision_amd.params import external_leaf_names
     hw = self.image_tower.grid(tuple(image_shape))
-    return external_leaf_names([l for e in self.entries("", hw, text_shape[1]) for l, _ in e.flax_leaves()],
-                               self.scan_prefixes())
+    return entry_leaf_names(self.entries("", hw, text_shape[1]), self.scan_prefixes())
 
   def make_store(self, image_shape, text_shape, device=None, frozen_leaves=()):
     """Allocates the flat parameter store for both towers (+ t, b).
 
     `frozen_leaves`: exact Flax leaf names that get no gradient / optimizer
-    state (config.schedule None entries); they are laid out last."""
-    device = device or torch.device("cuda", torch.cuda.current_device())
+    state (config.schedule None entries); they are laid out last (params.make_store)."""
     hw = self.image_tower.grid(tuple(image_shape))
-    ents = self.entries("", hw, text_shape[1])
-    from big_vision_amd.params import scan_name
-    frozen_leaves = set(frozen_leaves)
-    sp = self.scan_prefixes()
-    frozen = set()
-    for e in ents:
-      hits = [scan_name(leaf, sp)[0] in frozen_leaves for leaf, _ in e.flax_leaves()]
-      if any(hits) and not all(hits):
-        raise NotImplementedError(f"fused tensor {e.name} is only partially frozen")
-      if all(hits):
-        frozen.add(e.name)
-    return ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
+    return make_store(self.entries("", hw, text_shape[1]), device, self.scan_prefixes(), frozen_leaves)
 
   def init(self, rng, image, text=None, **kw):
     del kw
-    from big_vision_amd.models.vit import _seed_of
-    ishape = tuple(image[0].shape) if isinstance(image, (tuple, list)) else tuple(image.shape)
-    store = self.make_store(ishape, tuple(text.shape))
-    store.init_random(_seed_of(rng))
+    store = self.make_store(E.input_shape(image), tuple(text.shape))
+    store.init_random(E.seed_of(rng))
     store.refresh_shadow()
     return {"params": store.tree()}
 
@@ -328,23 +312,20 @@ class Model:
     if train and any(float(getattr(t, "dropout", 0.0) or 0.0) > 0.0 for t in (self.image_tower, self.text_tower)):
       if not rngs or "dropout" not in rngs:
         raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-      from big_vision_amd.models import vit as _vit
-      drop_key = _vit._seed_of(rngs["dropout"])
+      drop_key = E.seed_of(rngs["dropout"])
     params = variables["params"]
     if isinstance(params, ParamTree) and params.store is not None:
       store, prefix = params.store, params.prefix
     else:
       # two_towers.py:43: either input may be None.  The store holds BOTH towers' parameters, so the geometry of the
       # absent input is read off the tree itself (position-embedding lengths)
-      ishape = (tuple(image[0].shape) if isinstance(image, (tuple, list)) else tuple(image.shape)) if image is not None \
-          else self._image_shape_of(params)
+      ishape = E.input_shape(image) or self._image_shape_of(params)
       tshape = tuple(text.shape) if text is not None else (1, int(params["txt"]["pos_embedding"].shape[1]))
       store = adhoc_store(self._execs, ("two_towers", ishape[1:], tshape[1:], torch.cuda.current_device()),
                           params, lambda: self.make_store(ishape, tshape))
       prefix = ""
     store.refresh_shadow()
-    ishape = None if image is None else (tuple(image[0].shape) if isinstance(image, (tuple, list)) else tuple(image.shape))
-    ex = self.executor(store, prefix, ishape, None if text is None else tuple(text.shape))
+    ex = self.executor(store, prefix, E.input_shape(image), E.input_shape(text))
     zimg, ztxt, out, _ = ex.fwd(image, text, save=False, collect=collect, drop_key=drop_key)
     ex.check_inputs()
     return zimg, ztxt, out

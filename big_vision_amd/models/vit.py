@@ -53,14 +53,7 @@ def decode_variant(variant):
   }
 
 
-def _seed_of(rng) -> int:
-  if isinstance(rng, torch.Generator):
-    return int(rng.initial_seed())
-  a = np.asarray(rng).astype(np.uint64).ravel()
-  s = 0
-  for v in a:
-    s = (s * 1000003 + int(v)) % (2 ** 63)
-  return int(s)
+_seed_of = E.seed_of      # (its home is engine.py, next to Dropout; the name stays for the tests that use it)
 
 
 def dropout_for(rate, train, rngs):
@@ -70,7 +63,7 @@ def dropout_for(rate, train, rngs):
     return None
   if not rngs or "dropout" not in rngs:
     raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-  return E.Dropout(rate, _seed_of(rngs["dropout"]))
+  return E.Dropout(rate, E.seed_of(rngs["dropout"]))
 
 
 class VitExec:
@@ -239,7 +232,7 @@ class _Model:
     shape = tuple(image.shape)
     dev = image.device if torch.is_tensor(image) and image.is_cuda else torch.device("cuda", torch.cuda.current_device())
     store = ParamStore(self.entries("", self.grid(shape)), dev, scan_prefixes=self.scan_prefixes())
-    store.init_random(_seed_of(rng))
+    store.init_random(E.seed_of(rng))
     store.refresh_shadow()
     return {"params": store.tree()}
 

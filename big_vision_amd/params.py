@@ -15,6 +15,8 @@ GEMMs and the Adam moments), laid out for the kernels:
 
 `ParamStore.tree()` returns the nested dict with exactly the reference's leaf
 names and shapes; `load_tree()` accepts such a tree (e.g. from an .npz).
+`make_store(entries, device, scan_prefixes, frozen_leaves)` is how models and
+trainers build one; `entry_leaf_names` gives the names a config's regexes see.
 """
 from __future__ import annotations
 
@@ -417,6 +419,26 @@ class ParamStore:
 
   def zero_grad(self):
     self.ensure_grad().zero_()
+
+
+def entry_leaf_names(entries: Sequence[Entry], scan_prefixes: Sequence[str] = ()) -> List[str]:
+  """Names of the Flax leaves of `entries` as presented (stacked `encoderblock` below `scan_prefixes`)."""
+  return external_leaf_names([leaf for e in entries for leaf, _ in e.flax_leaves()], scan_prefixes)
+
+
+def make_store(entries: List[Entry], device=None, scan_prefixes: Sequence[str] = (), frozen_leaves=()) -> "ParamStore":
+  """The store of `entries` on `device` (default: the current GPU).  `frozen_leaves`: exact presented leaf names that
+  get no gradient / optimizer state (config.schedule None entries); their storage tensors are laid out last.  A fused
+  tensor (q/k/v) is frozen as a whole or not at all."""
+  device = device or torch.device("cuda", torch.cuda.current_device())
+  frozen_leaves, frozen = set(frozen_leaves), set()
+  for e in entries:
+    hits = [scan_name(leaf, scan_prefixes)[0] in frozen_leaves for leaf, _ in e.flax_leaves()]
+    if any(hits) and not all(hits):
+      raise NotImplementedError(f"fused tensor {e.name} is only partially frozen")
+    if all(hits):
+      frozen.add(e.name)
+  return ParamStore(entries, device, frozen=frozen, scan_prefixes=scan_prefixes)
 
 
 def adhoc_store(cache: dict, key, params, factory) -> "ParamStore":

@@ -18,6 +18,10 @@ every rank normalises its loss / dlogits by the GLOBAL batch size, so parameter
 gradients are partial sums and one all-reduce(SUM) finishes them (dp.GradSync).
 Mixup rolls the batch along dim 0 on every device independently, exactly like the
 reference's shard_map (:283-289).
+
+The host code around the kernels that every trainer shares lives here too (the SigLIP / contrastive, distillation and
+GSAM trainers call it): `make_optimizer` (the tail of a `make_train_state`), `prepare_batch`, `step_dropout`,
+`in_residual_stream`, `grad_sync`, `load_init`, `check_finite`.
 """
 from __future__ import annotations
 
@@ -30,8 +34,9 @@ from big_vision_amd import dp
 from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import optax as bv_optax
+from big_vision_amd import sharding
 from big_vision_amd import utils as u
-from big_vision_amd.params import ParamStore
+from big_vision_amd.params import entry_leaf_names, make_store
 
 F32 = torch.float32
 LOSSES = {"softmax_xent": ops.softmax_xent, "sigmoid_xent": ops.sigmoid_xent}
@@ -54,24 +59,9 @@ def _loss_kernel(config):
 def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_steps=None, device=None, after_init=None):
   """Parameter store + optimizer laid out for `config` (replaces train.py:191-262).  after_init(store): edits of the
   random init that a checkpoint load may still overwrite (a trainer's `init_head_bias`)."""
-  from big_vision_amd.models.vit import _seed_of
-  comm = comm or dp.Comm()
-  device = device or torch.device("cuda", torch.cuda.current_device())
-  hw = model.grid(tuple(image_shape))
-  from big_vision_amd.params import external_leaf_names, scan_name
-  ents = model.entries("", hw)
-  sp = model.scan_prefixes()
-  leaves = external_leaf_names([leaf for e in ents for leaf, _ in e.flax_leaves()], sp)
-  frozen_leaves = bv_optax.frozen_leaves(config, leaves)
-  frozen = set()
-  for e in ents:
-    hits = [scan_name(leaf, sp)[0] in frozen_leaves for leaf, _ in e.flax_leaves()]
-    if any(hits) and not all(hits):
-      raise NotImplementedError(f"fused tensor {e.name} is only partially frozen")
-    if all(hits):
-      frozen.add(e.name)
-  store = ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
-  store.init_random(_seed_of(rng))
+  ents, sp = model.entries("", model.grid(tuple(image_shape))), model.scan_prefixes()
+  store = make_store(ents, device, sp, bv_optax.frozen_leaves(config, entry_leaf_names(ents, sp)))
+  store.init_random(E.seed_of(rng))
   if after_init is not None:
     after_init(store)
     store.mark_dirty()
@@ -79,13 +69,23 @@ def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_step
     _load_model_init(model, config, store)
   store.refresh_shadow()
   store.want_grads = True
-  from big_vision_amd import sharding     # train.py:201-203: replicate, or fsdp = sharded optimizer state / update
-  fsdp = sharding.is_sharded(sharding.check_config(config, store.tree(), mesh=comm))
-  batch_size = config.get("input", {}).get("batch_size", image_shape[0] * comm.size)
-  total_steps = total_steps if total_steps is not None else u.steps("total", config, None, batch_size)
-  opt, sched_fns = bv_optax.make(config, store, sched_kw=dict(total_steps=total_steps, batch_size=batch_size,
-                                                               data_size=None), comm=comm, shard=fsdp)
+  opt, sched_fns = make_optimizer(config, store, image_shape[0], comm, total_steps)
   return {"params": store.tree(), "opt": opt}, sched_fns
+
+
+def make_optimizer(config, store, n_local, comm=None, total_steps=None):
+  """(opt, sched_fns) of `config` on `store`, the tail of every trainer's make_train_state (train.py:201-218): the
+  parameter placement - replicated, or "fsdp" somewhere in config.sharding_strategy = sharded optimizer state / update;
+  any other strategy is refused, not ignored - the global batch size (`n_local` per rank unless config.input says
+  otherwise), the number of steps and `bv_optax.make`.  Take `store.tree()` only AFTER this call: the fsdp placement
+  shards the fp32 master here, and a tree built before it would keep the whole unsharded master alive through stale
+  views."""
+  comm = comm or dp.Comm()
+  fsdp = sharding.is_sharded(sharding.check_config(config, store.tree(), mesh=comm))
+  batch_size = config.get("input", {}).get("batch_size", n_local * comm.size)
+  total_steps = total_steps if total_steps is not None else u.steps("total", config, None, batch_size)
+  return bv_optax.make(config, store, sched_kw=dict(total_steps=total_steps, batch_size=batch_size, data_size=None),
+                       comm=comm, shard=fsdp)
 
 
 def _load_model_init(model, config, store):
@@ -130,17 +130,27 @@ def mixup_p(config):
   return float(config.get("mixup", {}).get("p", 0.0) or 0.0) if config.get("mixup") else 0.0
 
 
-def prepare_batch(batch, rng, opt, mix_p):
-  """fp32 contiguous (images, labels) of `batch`, mixed up when `mix_p` (train.py:283-289): one coefficient per step
-  (fold_in(rng, step), or the batch's own `mixup_a`), the roll is per device."""
-  images = batch["image"].to(F32).contiguous()
-  labels = batch["labels"].to(F32).contiguous()
+def prepare_batch(batch, rng, opt, mix_p, keys=("image", "labels")):
+  """`batch` with every one of `keys` that is present fp32 contiguous, and mixed up when `mix_p` (train.py:283-289):
+  ONE coefficient per step for all of them (fold_in(rng, step), or the batch's own `mixup_a`), the roll is per
+  device.  Returns a dict; its other entries are the batch's."""
+  data = dict(batch)
+  keys = [k for k in keys if k in data]
+  for k in keys:
+    data[k] = data[k].to(F32).contiguous()
   if mix_p:
-    a = batch.get("mixup_a") if isinstance(batch, dict) else None
+    a = data.get("mixup_a")
     if a is None:
       a = u.get_mixup_coefficient(rng, bv_optax.get_count(opt), mix_p)
-    images, labels = ops.mixup(images, a), ops.mixup(labels, a)
-  return images, labels
+    for k in keys:
+      data[k] = ops.mixup(data[k], a)
+  return data
+
+
+def images_labels(batch, rng, opt, mix_p):
+  """`prepare_batch` of the classification trainers: the (images, labels) pair, both required."""
+  data = prepare_batch(batch, rng, opt, mix_p)
+  return data["image"], data["labels"]
 
 
 def step_dropout(model, rng, opt, comm):
@@ -150,13 +160,15 @@ def step_dropout(model, rng, opt, comm):
     return None
   if rng is None:
     raise ValueError("the model has dropout > 0: update_fn needs an rng")
-  from big_vision_amd.models.vit import _seed_of
-  return E.Dropout(model.dropout, _seed_of(rng)).fold("step", int(bv_optax.get_count(opt)), "rank", int(comm.rank))
+  return E.Dropout(model.dropout, E.seed_of(rng)).fold("step", int(bv_optax.get_count(opt)), "rank", int(comm.rank))
 
 
 def in_residual_stream(config, fn):
   """`fn` run on config.residual_stream ("float32" = the reference's arithmetic, "bfloat16"): set for the duration of
-  each call and restored afterwards, so model.apply / other trainers in the process keep their own."""
+  each call and restored afterwards, so model.apply / other trainers in the process keep their own.  Without a config
+  `fn` runs on whatever stream its caller has set: it is returned as it is."""
+  if config is None:
+    return fn
   stream = config.get("residual_stream", "float32")
 
   def wrapped(*args, **kw):
@@ -166,6 +178,12 @@ def in_residual_stream(config, fn):
     finally:
       E.set_residual_stream(old)
   return wrapped
+
+
+def grad_sync(opt, comm, store):
+  """The overlapped gradient sum of one step: the sharded optimizer's own ("fsdp" placement: every range is summed
+  onto its owner only, dp.GradShardSync), else the all-reduce of the whole gradient buffer (dp.GradSync)."""
+  return opt.grad_sync() if getattr(opt, "sharded", False) else dp.GradSync(comm, store.grad)
 
 
 def make_update_fn(model, config, comm=None):
@@ -180,17 +198,14 @@ def make_update_fn(model, config, comm=None):
     store.want_grads = True
     store.refresh_shadow()   # no-op when clean; picks up load_tree() / in-place master edits
     store.zero_grad()
-    images, labels = prepare_batch(batch, rng, opt, mix_p)
+    images, labels = images_labels(batch, rng, opt, mix_p)
     n = images.shape[0]
     ex = model.executor(store, "", model.grid(tuple(images.shape)))
     drop = step_dropout(model, rng, opt, comm)
     logits, _, ctx = ex.fwd(images, save=True, drop=drop)
     acc = torch.zeros(1, device=images.device, dtype=torch.float64)
     dlogits = loss_kernel(logits.contiguous(), labels, acc, want_grad=True, n_global=n * comm.size)
-    # ("fsdp" placement: every range is summed onto its owner only, dp.GradShardSync)
-    sync = None
-    if comm.size > 1:
-      sync = opt.grad_sync() if getattr(opt, "sharded", False) else dp.GradSync(comm, store.grad)
+    sync = grad_sync(opt, comm, store) if comm.size > 1 else None
     ex.bwd(ctx, dlogits)
     if sync is not None:
       sync.finish()
@@ -206,17 +221,9 @@ def make_predict_fn(model, config=None):
   """`predict_fn(train_state, batch) -> (logits, out)` (`eval_logits_fn`, train.py:380-382): the forward at train=False on the same
   kernels as the training step, for `evaluators.common.from_config(config, {"predict": predict_fn})`.  With `config`
   the forward runs on `config.residual_stream`, like `update_fn`; it reads the parameters and changes nothing."""
-  stream = config.get("residual_stream", "float32") if config is not None else None
-
   def predict_fn(train_state, batch):
-    old = E.set_residual_stream(stream) if stream is not None else None
-    try:
-      logits, out = model.apply({"params": train_state["params"]}, batch["image"].to(F32).contiguous())
-    finally:
-      if stream is not None:
-        E.set_residual_stream(old)
-    return logits, out
-  return predict_fn
+    return model.apply({"params": train_state["params"]}, batch["image"].to(F32).contiguous())
+  return in_residual_stream(config, predict_fn)
 
 
 def check_finite(measurements):

@@ -33,7 +33,7 @@ from big_vision_amd import ops
 from big_vision_amd import optax as bv_optax
 from big_vision_amd import train as bv_train
 from big_vision_amd import utils as u
-from big_vision_amd.params import ParamStore
+from big_vision_amd.params import entry_leaf_names, make_store
 
 F32 = torch.float32
 
@@ -63,29 +63,14 @@ def _image_shape(image_shapes, name):
 
 def make_train_state(models, config, image_shapes, *, rng=0, comm=None, total_steps=None, device=None):
   """Student store + optimizer (as train.make_train_state) and one frozen, loaded store per teacher."""
-  from big_vision_amd.models.vit import _seed_of
-  from big_vision_amd.params import external_leaf_names, scan_name
-  from big_vision_amd import sharding
-  comm = comm or dp.Comm()
-  device = device or torch.device("cuda", torch.cuda.current_device())
-  seed = _seed_of(rng)
+  seed = E.seed_of(rng)
   for name in config.teachers:       # a teacher NEEDS an init: fail before anything is allocated
     config[f"{name}_init"]   # pylint: disable=pointless-statement
   # -- student
   model = models["student"]
   shape = _image_shape(image_shapes, "student")
-  ents = model.entries("", model.grid(shape))
-  sp = model.scan_prefixes()
-  leaves = external_leaf_names([leaf for e in ents for leaf, _ in e.flax_leaves()], sp)
-  frozen_leaves = bv_optax.frozen_leaves(config, leaves)
-  frozen = set()
-  for e in ents:
-    hits = [scan_name(leaf, sp)[0] in frozen_leaves for leaf, _ in e.flax_leaves()]
-    if any(hits) and not all(hits):
-      raise NotImplementedError(f"fused tensor {e.name} is only partially frozen")
-    if all(hits):
-      frozen.add(e.name)
-  store = ParamStore(ents, device, frozen=frozen, scan_prefixes=sp)
+  ents, sp = model.entries("", model.grid(shape)), model.scan_prefixes()
+  store = make_store(ents, device, sp, bv_optax.frozen_leaves(config, entry_leaf_names(ents, sp)))
   store.init_random(seed)
   if "init_head_bias" in config:
     store.leaf("head/bias").fill_(float(config["init_head_bias"]))
@@ -100,20 +85,14 @@ def make_train_state(models, config, image_shapes, *, rng=0, comm=None, total_st
   for i, name in enumerate(config.teachers):
     m = models[name]
     hw = m.grid(_image_shape(image_shapes, name))
-    ts = ParamStore(m.entries("", hw), device, scan_prefixes=m.scan_prefixes())
+    ts = make_store(m.entries("", hw), device, m.scan_prefixes())
     ts.init_random(seed + 1 + i)
     bv_train.load_init(m, ts, config[f"{name}_init"], config.get(name), config.get(f"{name}_load", {}),
                        key=f"{name}_init")
     ts.refresh_shadow()
     params[name] = ts.tree()
-  fsdp = sharding.is_sharded(sharding.check_config(config, store.tree(), mesh=comm))
-  batch_size = config.get("input", {}).get("batch_size", shape[0] * comm.size)
-  total_steps = total_steps if total_steps is not None else u.steps("total", config, None, batch_size)
-  opt, sched_fns = bv_optax.make(config, store, sched_kw=dict(total_steps=total_steps, batch_size=batch_size,
-                                                               data_size=None), comm=comm, shard=fsdp)
-  # the student's tree is taken AFTER the optimizer is made, as in train.make_train_state: the fsdp placement shards
-  # the fp32 master there, and a tree built before it would keep the whole unsharded master alive through stale views
-  return {"params": {"student": store.tree(), **params}, "opt": opt}, sched_fns
+  opt, sched_fns = bv_train.make_optimizer(config, store, shape[0], comm, total_steps)
+  return {"params": {"student": store.tree(), **params}, "opt": opt}, sched_fns     # (the tree only now: make_optimizer)
 
 
 def _distance(config):
@@ -140,11 +119,10 @@ def _fwd(model, params, image, **kw):
 
 def make_update_fn(models, config, comm=None):
   """Builds `update_fn(train_state, rng, batch)` (distill.py:250-285)."""
-  from big_vision_amd.models.vit import _seed_of
   comm = comm or dp.Comm()
   kind, dist_kw = _distance(config)
   teachers = tuple(config.teachers)
-  mix_p = float(config.get("mixup", {}).get("p", 0.0) or 0.0) if config.get("mixup") else 0.0
+  mix_p = bv_train.mixup_p(config)
 
   def update_fn(train_state, rng, batch):
     params, opt = train_state["params"], train_state["opt"]
@@ -153,17 +131,8 @@ def make_update_fn(models, config, comm=None):
     store.want_grads = True
     store.refresh_shadow()
     store.zero_grad()
-    data = dict(batch)
-    mixable = [k for k in ("image", "labels") + tuple(models) if k in data]
-    for k in mixable:
-      data[k] = data[k].to(F32).contiguous()
-    if mix_p:
-      # distill.py:257-261: ONE coefficient for the images, the labels and every per-model input; the roll is per device
-      a = data.get("mixup_a")
-      if a is None:
-        a = u.get_mixup_coefficient(rng, bv_optax.get_count(opt), mix_p)
-      for k in mixable:
-        data[k] = ops.mixup(data[k], a)
+    # distill.py:257-261: ONE coefficient for the images, the labels and every per-model input
+    data = bv_train.prepare_batch(batch, rng, opt, mix_p, keys=("image", "labels") + tuple(models))
     n = getfirst(data, "student", "image").shape[0]
     n_global = n * comm.size
     dev = store.device
@@ -182,11 +151,7 @@ def make_update_fn(models, config, comm=None):
     for name in teachers:
       t_logits[name] = _fwd(models[name], params[name], getfirst(data, name, "image"), save=False)[0].contiguous()
     # student: train mode, its own dropout key per step and rank (distill.py:264-267)
-    drop = None
-    if float(getattr(student, "dropout", 0.0) or 0.0) > 0.0:
-      if rng is None:
-        raise ValueError("the student has dropout > 0: update_fn needs an rng")
-      drop = E.Dropout(student.dropout, _seed_of(rng)).fold("step", int(bv_optax.get_count(opt)), "rank", int(comm.rank))
+    drop = bv_train.step_dropout(student, rng, opt, comm)
     logits, _, ctx = _fwd(student, params["student"], getfirst(data, "student", "image"), save=True, drop=drop)
     logits = logits.contiguous()
     measure("student", logits)
@@ -199,9 +164,7 @@ def make_update_fn(models, config, comm=None):
       _, g = ops.distill_dist(kind, logits, t_logits[name], loss_sum=meas[f"distill_loss_{name}"], dstudent=dlogits,
                               want_grad=True, n_global=n_global, **dist_kw)
       dlogits = g
-    sync = None
-    if comm.size > 1:
-      sync = opt.grad_sync() if getattr(opt, "sharded", False) else dp.GradSync(comm, store.grad)
+    sync = bv_train.grad_sync(opt, comm, store) if comm.size > 1 else None
     student.executor(store, "", student.grid(tuple(getfirst(data, "student", "image").shape))).bwd(ctx, dlogits)
     if sync is not None:
       sync.finish()
@@ -214,15 +177,7 @@ def make_update_fn(models, config, comm=None):
     measurements.update(opt.step())
     return {"params": params, "opt": opt}, measurements
 
-  stream = config.get("residual_stream", "float32")
-
-  def update_fn_in_stream(train_state, rng, batch):
-    old = E.set_residual_stream(stream)
-    try:
-      return update_fn(train_state, rng, batch)
-    finally:
-      E.set_residual_stream(old)
-  return update_fn_in_stream
+  return bv_train.in_residual_stream(config, update_fn)
 
 
 def make_predict_fns(models, config):

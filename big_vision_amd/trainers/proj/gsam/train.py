@@ -82,7 +82,7 @@ def make_grad_fn(model, config, comm=None):
       bufs[:] = [gsam.Buffers(store)]
     store.want_grads = True
     store.refresh_shadow()
-    images, labels = bv_train.prepare_batch(batch, rng, opt, mix_p)     # mixup once, before both passes
+    images, labels = bv_train.images_labels(batch, rng, opt, mix_p)     # mixup once, before both passes
     n = images.shape[0]
     ex = model.executor(store, "", model.grid(tuple(images.shape)))
     drop = bv_train.step_dropout(model, rng, opt, comm)                 # the same key in both passes

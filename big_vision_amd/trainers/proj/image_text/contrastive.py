@@ -34,22 +34,11 @@ LOSSES = ("softmax", "sigmoid", "chunked_sigmoid")
 
 
 def sigmoid_loss(zimg, ztxt, t_param, b_param, comm: dp.Comm, chunked=False):
-  """-> (stats f64[3] = [loss share, dL/dt', dL/db], dzimg, dztxt, extras) on this rank's embeddings."""
-  n, E = zimg.shape
-  B = n * comm.size
-  ztxt_all = comm.all_gather_rows(ztxt)
-  raw = torch.empty((n, B), device=zimg.device, dtype=F32)
-  ops.sgemm(zimg, E, 1, ztxt_all, 1, E, raw, n, B, E)
-  ls = ops.logit_stats(raw, t_param, b_param, comm.rank * n)        # before raw becomes dL/dS
+  """-> (stats f64[3] = [loss share, dL/dt', dL/db], dzimg, dztxt, extras) on this rank's embeddings: the sigmoid
+  loss of trainers.proj.image_text.siglip with its logit statistics as extras (chunked: without the global negative
+  statistics)."""
   names = ops.LOGIT_STATS_NAMES[:6] if chunked else ops.LOGIT_STATS_NAMES
-  extras = {k: ls[i] for i, k in enumerate(names)}
-  stats = torch.zeros(3, device=zimg.device, dtype=torch.float64)
-  ops.siglip_loss_(raw, t_param, b_param, stats, comm.rank * n, B)
-  dzimg = torch.empty((n, E), device=zimg.device, dtype=F32)
-  ops.sgemm(raw, B, 1, ztxt_all, E, 1, dzimg, n, E, B, log_alpha=t_param)
-  dztxt_all = torch.empty((B, E), device=zimg.device, dtype=F32)
-  ops.sgemm(raw, 1, B, zimg, E, 1, dztxt_all, B, E, n, log_alpha=t_param)
-  return stats, dzimg, comm.reduce_scatter_rows(dztxt_all), extras
+  return _siglip.sigmoid_loss_fwd_bwd(zimg, ztxt, t_param, b_param, comm, logit_stats=names)
 
 
 def chunked_sigmoid_loss(zimg, ztxt, t_param, b_param, comm: dp.Comm):

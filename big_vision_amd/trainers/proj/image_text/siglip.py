@@ -14,6 +14,9 @@ rows [r*n, (r+1)*n) of zimg and ztxt.  all_gather(ztxt) -> local logits
 [n, B] with the positive diagonal at column r*n + i -> G = dL/dS with the GLOBAL
 1/B -> dzimg local, dztxt_partial [B, E] -> reduce_scatter -> all parameter
 gradients are partial sums of the global gradient -> all_reduce(SUM).
+
+The optimizer tail of `make_train_state`, the residual-stream wrapper of the step and of `predict_fn`, the choice of
+the gradient sync and `check_finite` are `big_vision_amd.train`'s.
 """
 from __future__ import annotations
 
@@ -25,32 +28,33 @@ from big_vision_amd import dp
 from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import optax as bv_optax
-from big_vision_amd import utils as u
+from big_vision_amd import train as bv_train
+from big_vision_amd.train import check_finite  # noqa: F401  (the trainer's surface; siglip.py:468-470)
 
 F32 = torch.float32
-
-
-def _img_shape(images):
-  """Shape that keys the image tower's layout: [n, H, W, 3] pixels, or - NaFlex
-  (models/proj/image_text/naflex_vit.py:227) - the patches of the (patches, ptype, yabs, xabs) tuple."""
-  return tuple(images[0].shape) if isinstance(images, (tuple, list)) else tuple(images.shape)
 
 
 def _img_slice(images, a, b):
   return tuple(t[a:b] for t in images) if isinstance(images, (tuple, list)) else images[a:b]
 
 
-def sigmoid_loss_fwd_bwd(zimg, ztxt, t_param, b_param, comm: dp.Comm):
+def sigmoid_loss_fwd_bwd(zimg, ztxt, t_param, b_param, comm: dp.Comm, logit_stats=None):
   """Global-batch pairwise sigmoid loss (siglip.py:291-306) and its gradients.
 
   zimg, ztxt: this rank's L2-normalised embeddings [n, E] (fp32).
-  Returns (stats f64[3] = [loss share, dL/dt', dL/db], dzimg [n,E], dztxt [n,E]).
+  Returns (stats f64[3] = [loss share, dL/dt', dL/db], dzimg [n,E], dztxt [n,E]).  logit_stats: names (a prefix of
+  ops.LOGIT_STATS_NAMES) of the per-device logit statistics to report; the result then has a fourth item, the dict of
+  them, from one bv_logit_stats pass over the logits before the loss kernel overwrites them.
   """
   n, E = zimg.shape
   B = n * comm.size
   ztxt_all = comm.all_gather_rows(ztxt)
   raw = torch.empty((n, B), device=zimg.device, dtype=F32)
   ops.sgemm(zimg, E, 1, ztxt_all, 1, E, raw, n, B, E)                       # zimg . ztxt_all^T
+  extras = ()
+  if logit_stats is not None:
+    ls = ops.logit_stats(raw, t_param, b_param, comm.rank * n)              # before raw becomes dL/dS
+    extras = ({k: ls[i] for i, k in enumerate(logit_stats)},)
   stats = torch.zeros(3, device=zimg.device, dtype=torch.float64)
   ops.siglip_loss_(raw, t_param, b_param, stats, comm.rank * n, B)            # raw := G
   dzimg = torch.empty((n, E), device=zimg.device, dtype=F32)
@@ -58,7 +62,7 @@ def sigmoid_loss_fwd_bwd(zimg, ztxt, t_param, b_param, comm: dp.Comm):
   dztxt_all = torch.empty((B, E), device=zimg.device, dtype=F32)
   ops.sgemm(raw, 1, B, zimg, E, 1, dztxt_all, B, E, n, log_alpha=t_param)    # t G^T zimg
   dztxt = comm.reduce_scatter_rows(dztxt_all)
-  return stats, dzimg, dztxt
+  return (stats, dzimg, dztxt) + extras
 
 
 def loss_fn(model, params, images, labels, comm=None):
@@ -74,22 +78,12 @@ def loss_fn(model, params, images, labels, comm=None):
 def make_train_state(model, config, image_shape, text_shape, *, rng=0, comm=None, total_steps=None,
                      device=None):
   """Parameter store + optimizer laid out for `config` (replaces siglip.py:190-260)."""
-  from big_vision_amd.models.vit import _seed_of
-  comm = comm or dp.Comm()
   frozen = bv_optax.frozen_leaves(config, model.leaf_names(image_shape, text_shape))
   store = model.make_store(image_shape, text_shape, device=device, frozen_leaves=frozen)
-  store.init_random(_seed_of(rng))
+  store.init_random(E.seed_of(rng))
   store.refresh_shadow()
   store.want_grads = True
-  # parameter placement (siglip.py:196, 232-237): replicated; any other strategy is refused, not ignored
-  from big_vision_amd import sharding
-  specs = sharding.check_config(config, store.tree(), mesh=comm)
-  fsdp = sharding.is_sharded(specs)   # "fsdp" somewhere in config.sharding_strategy: sharded optimizer state / update
-  batch_size = config.get("input", {}).get("batch_size", image_shape[0] * comm.size)
-  total_steps = total_steps if total_steps is not None else u.steps(
-      "total", config, None, batch_size)
-  sched_kw = dict(total_steps=total_steps, batch_size=batch_size, data_size=None)
-  opt, sched_fns = bv_optax.make(config, store, sched_kw=sched_kw, comm=comm, shard=fsdp)
+  opt, sched_fns = bv_train.make_optimizer(config, store, image_shape[0], comm, total_steps)   # (siglip.py:196, 232-237)
   return {"params": store.tree(), "opt": opt}, sched_fns
 
 
@@ -124,8 +118,7 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
     if towers_drop:
       if rng is None:
         raise ValueError("the model has dropout > 0: update_fn needs an rng")
-      from big_vision_amd.models import vit as _vit
-      step_key = E.Dropout(0.0, _vit._seed_of(rng)).key("step", int(opt.count), "rank", int(comm.rank))
+      step_key = E.Dropout(0.0, E.seed_of(rng)).key("step", int(opt.count), "rank", int(comm.rank))
     drop_key = lambda s: None if step_key is None else E.Dropout(0.0, step_key).key("microbatch", int(s))
     store = params.store
     store.want_grads = True
@@ -133,8 +126,8 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
     # marks the bf16 shadow dirty; forward and backward read the shadow (no-op when clean)
     store.refresh_shadow()
     store.zero_grad()
-    n = _img_shape(images)[0]
-    ex = model.executor(store, "", _img_shape(images), tuple(labels.shape))
+    n = E.input_shape(images)[0]
+    ex = model.executor(store, "", E.input_shape(images), tuple(labels.shape))
     # default since round 6: the text tower on a side stream beside the image tower (TwoTowersExec; the towers share
     # nothing until the loss, two_towers.py:56-75; same kernels on the same inputs, identical results).
     # config.tower_streams = 1 puts both towers back on the caller's stream.
@@ -151,7 +144,7 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
     # (comm.active: N > 1 ranks, or a ONE-rank group with forced collectives - bench.py's rank512_rccl and
     # tests/test_dp_nccl_gpu.py run the overlapped path, CU reservation included, exactly as N > 1 does)
     overlap = comm.active and config.get("overlap_grad_sync", True)
-    sync = (opt.grad_sync() if sharded else dp.GradSync(comm, store.grad)) if overlap else None
+    sync = bv_train.grad_sync(opt, comm, store) if overlap else None
 
     if micro and n > micro:
       assert n % micro == 0, f"per-device batch {n} not divisible by microbatch {micro}"
@@ -265,17 +258,7 @@ def make_update_fn(model, config, comm=None, loss_fwd_bwd=None, measure=None):
     measurements.update(opt.step())
     return {"params": params, "opt": opt}, measurements
 
-  # config.residual_stream ("float32" = the reference's arithmetic, "bfloat16"): set for the duration of
-  # each step and restored afterwards, so model.apply / other trainers in the process keep their own
-  stream = config.get("residual_stream", "float32")
-  inner = update_fn
-
-  def update_fn(train_state, rng, batch):
-    old = E.set_residual_stream(stream)
-    try:
-      return inner(train_state, rng, batch)
-    finally:
-      E.set_residual_stream(old)
+  update_fn = bv_train.in_residual_stream(config, update_fn)
   update_fn.state_cache = state_cache   # diagnostics: how many micro-batches keep their activations
   return update_fn
 
@@ -284,25 +267,10 @@ def make_predict_fn(model, config=None):
   """`predict_fn(train_state, batch)` handed to the evaluators (siglip.py:388-392): either of
   batch["image"] / batch["labels"] may be missing.  With `config` the forward runs on `config.residual_stream`,
   like `update_fn` (and like train.make_predict_fn); it reads the parameters and changes nothing."""
-  stream = config.get("residual_stream", "float32") if config is not None else None
-
   def predict_fn(train_state, batch):
-    old = E.set_residual_stream(stream) if stream is not None else None
-    try:
-      zimg, ztxt, out = model.apply({"params": train_state["params"]}, batch.get("image", None),
-                                    batch.get("labels", None), collect=False)
-    finally:
-      if stream is not None:
-        E.set_residual_stream(old)
-    return zimg, ztxt, out
-  return predict_fn
-
-
-def check_finite(measurements):
-  """NaN/Inf abort of siglip.py:468-470 (synchronises)."""
-  for k, v in measurements.items():
-    if not torch.isfinite(torch.as_tensor(v)).all():
-      raise RuntimeError(f"measurement '{k}' is not finite: {v}")
+    return model.apply({"params": train_state["params"]}, batch.get("image", None), batch.get("labels", None),
+                       collect=False)
+  return bv_train.in_residual_stream(config, predict_fn)
 
 
 def get_model(config):

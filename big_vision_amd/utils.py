@@ -18,6 +18,8 @@ from collections.abc import Mapping
 
 import numpy as np
 
+from big_vision_amd.engine import seed_of
+
 
 # ------------------------------------------------------------- tree utils ----
 def _traverse_with_names(tree, with_inner_nodes=False):
@@ -287,8 +289,7 @@ def get_mixup_coefficient(rng, step, p):
   jax.random with the step-folded key; here a host torch.Generator seeded from (rng, step)
   plays that role (same distribution, not the same bits - tests pass `mixup_a` explicitly)."""
   import torch
-  from big_vision_amd.models.vit import _seed_of
-  g = torch.Generator().manual_seed((_seed_of(rng if rng is not None else 0) * 1000003 + int(step)) % (2 ** 63 - 1))
+  g = torch.Generator().manual_seed((seed_of(rng if rng is not None else 0) * 1000003 + int(step)) % (2 ** 63 - 1))
   # Beta(p, p) = first coordinate of Dirichlet(p, p); the only sampler that takes a Generator
   a = float(torch._sample_dirichlet(torch.tensor([float(p), float(p)]), generator=g)[0].item())
   return max(a, 1.0 - a)

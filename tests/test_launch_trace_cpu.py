@@ -18,6 +18,7 @@ import ctypes
 import json
 import os
 import sys
+import tempfile
 from unittest import mock
 
 import pytest
@@ -28,11 +29,15 @@ if os.path.dirname(HERE) not in sys.path:
   sys.path.insert(0, os.path.dirname(HERE))
 
 from big_vision_amd import _lib, engine as E, ops, train  # noqa: E402
+from big_vision_amd import utils as u  # noqa: E402
 from big_vision_amd.compat.ml_collections import ConfigDict  # noqa: E402
 from big_vision_amd.models import vit  # noqa: E402
+from big_vision_amd.models.proj.clippo import one_tower  # noqa: E402
 from big_vision_amd.models.proj.image_text import naflex_vit, text_transformer, two_towers  # noqa: E402
 from big_vision_amd.params import ParamStore  # noqa: E402
-from big_vision_amd.trainers.proj.image_text import siglip  # noqa: E402
+from big_vision_amd.trainers.proj.distill import distill  # noqa: E402
+from big_vision_amd.trainers.proj.gsam import train as gsam_train  # noqa: E402
+from big_vision_amd.trainers.proj.image_text import contrastive, siglip  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "launch_trace")
 
@@ -116,29 +121,90 @@ def _cfg(**kw):
   return c
 
 
-def _siglip(config, image=IMG, text=TXT, n=8, rng=None, apply_collect=False, **model_kw):
+def _siglip(config, image=IMG, text=TXT, n=8, rng=None, apply_collect=False, trainer=siglip, predict=False, clippo=False,
+            **model_kw):
+  """One step of `trainer` (siglip | contrastive), or its predict function; clippo: on the one-tower model, whose
+  caption is an image of the photo's geometry."""
   def case():
-    model = two_towers.Model(image=image, text=text, out_dim=(None, 64), temperature_init=10.0, bias_init=-10.0, **model_kw)
+    if clippo:
+      model = one_tower.Model(image=image, out_dim=64)
+    else:
+      model = two_towers.Model(image=image, text=text, out_dim=(None, 64), temperature_init=10.0, bias_init=-10.0,
+                               **model_kw)
     images = torch.zeros((n, 32, 32, 3))
-    labels = torch.ones((n, 8), dtype=torch.int32)
-    state, _ = siglip.make_train_state(model, config, tuple(images.shape), tuple(labels.shape), rng=0, total_steps=10,
-                                       device="cpu")
+    labels = torch.zeros((n, 32, 32, 3)) if clippo else torch.ones((n, 8), dtype=torch.int32)
+    state, _ = trainer.make_train_state(model, config, tuple(images.shape), tuple(labels.shape), rng=0, total_steps=10,
+                                        device="cpu")
     if apply_collect:
       return lambda: model.apply({"params": state["params"]}, images, labels, train=True, collect=True,
                                  rngs={"dropout": rng})
-    fn = siglip.make_update_fn(model, config)
+    if predict:
+      fn = trainer.make_predict_fn(model, config)
+      return lambda: fn(state, {"image": images, "labels": labels})
+    fn = trainer.make_update_fn(model, config)
     return lambda: fn(state, rng, {"image": images, "labels": labels})
   return case
 
 
-def _vit_cls(num_classes=16, **model):
+def _gsam_read_back():
+  """The GSAM vector stage reads |g_clean|^2 and (<g_robust, g_clean>, |g_robust|^2) back from fp64 accumulators,
+  which a dry run leaves at zero, and divides by them: the two read-backs return fixed non-zero values instead."""
+  item, tolist = torch.Tensor.item, torch.Tensor.tolist
+  return (mock.patch.object(torch.Tensor, "item", lambda t: 4.0 if t.dtype == torch.float64 else item(t)),
+          mock.patch.object(torch.Tensor, "tolist", lambda t: [1.0, 2.0] if t.dtype == torch.float64 else tolist(t)))
+
+
+def _vit_cls(num_classes=16, cfg=None, rng=0, batch=None, trainer=train, predict=False, read_back=False, **model):
+  """One step of `trainer` (train | the GSAM trainer) on the tiny ViT, or its predict function."""
   def case():
-    cfg = _cfg(model_name="vit", num_classes=num_classes, loss="softmax_xent",
-               model=dict(patch_size=(16, 16), **TINY, **model))
-    _, m = train.get_model(cfg)
-    state, _ = train.make_train_state(m, cfg, (2, 32, 32, 3), rng=0, total_steps=10, device="cpu")
-    fn = train.make_update_fn(m, cfg)
-    return lambda: fn(state, 0, {"image": torch.zeros((2, 32, 32, 3)), "labels": torch.zeros((2, num_classes))})
+    config = _cfg(model_name="vit", num_classes=num_classes, loss="softmax_xent",
+                  model=dict(patch_size=(16, 16), **TINY, **model), **(cfg or {}))
+    _, m = trainer.get_model(config)
+    state, _ = trainer.make_train_state(m, config, (2, 32, 32, 3), rng=0, total_steps=10, device="cpu")
+    data = {"image": torch.zeros((2, 32, 32, 3)), "labels": torch.zeros((2, num_classes)), **(batch or {})}
+    if predict:
+      fn = trainer.make_predict_fn(m, config)
+      return lambda: fn(state, data)
+    fn = trainer.make_update_fn(m, config)
+
+    def run():
+      with contextlib.ExitStack() as st:
+        for patch in (_gsam_read_back() if read_back else ()):
+          st.enter_context(patch)
+        fn(state, rng, data)
+    return run
+  return case
+
+
+def _distill(teachers, cfg=None, rng=0, labels=True, batch=None, shapes=None, predict=None, **student):
+  """One step of the distillation trainer, or the predict function named `predict`.  Teacher i is a ViT of depth 1 + i
+  whose checkpoint is written to a temporary directory and loaded by make_train_state."""
+  n, classes = 4, 10
+
+  def case():
+    config = _cfg(num_classes=classes, student_name="vit", student=dict(patch_size=(16, 16), **TINY, **student),
+                  teachers=list(teachers), **(cfg or {}))
+    for i, t in enumerate(teachers):
+      config[f"{t}_name"], config[t] = "vit", dict(patch_size=(16, 16), **dict(TINY, depth=1 + i))
+    models = distill.get_models(config)
+    image_shapes = {"image": (n, 32, 32, 3), **(shapes or {})}
+    with tempfile.TemporaryDirectory() as tmp:
+      for t in teachers:
+        m = models[t]
+        store = ParamStore(m.entries("", m.grid(tuple(image_shapes.get(t, image_shapes["image"])))), "cpu")
+        store.init_random(7)
+        config[f"{t}_init"] = os.path.join(tmp, f"{t}.npz")
+        u.save_params_npz(config[f"{t}_init"], {"params": store.tree()})
+      state, _ = distill.make_train_state(models, config, image_shapes, rng=0, total_steps=10, device="cpu")
+    data = {k: torch.zeros(s) for k, s in image_shapes.items()}
+    if labels:
+      data["labels"] = torch.zeros((n, classes))
+    data.update(batch or {})
+    if predict:
+      fn = distill.make_predict_fns(models, config)[predict]
+      return lambda: fn(state, data)
+    fn = distill.make_update_fn(models, config)
+    return lambda: fn(state, rng, data)
   return case
 
 
@@ -194,6 +260,9 @@ def _vit_collect(num_classes=None, **kw):
 
 DROP = dict(image=dict(IMG, dropout=0.1), text=dict(TXT, dropout=0.1), rng=7)
 MB = dict(microbatch=2)
+MIXUP = dict(cfg=dict(mixup=dict(p=0.2, fold_in=None)), batch=dict(mixup_a=0.75))    # (the batch's own coefficient)
+BF16 = dict(residual_stream="bfloat16")
+GSAM = dict(rho_max=0.6, rho_min=0.1, alpha=0.6, lr_max=1e-3, lr_min=1e-5)
 
 CASES = {
     # SigLIP step: one pass; two passes over 4 micro-batches with every keep / context-kind scheme
@@ -219,6 +288,28 @@ CASES = {
     "vit_cls_map": _vit_cls(pool_type="map"),
     "vit_cls_gap_rep12_classes10": _vit_cls(num_classes=10, pool_type="gap", rep_size=12, posemb="sincos2d"),
     "vit_cls_tok_rep_true": _vit_cls(pool_type="tok", rep_size=True),
+    "vit_cls_mixup_dropout": _vit_cls(pool_type="gap", dropout=0.1, rng=7, **MIXUP),
+    "vit_cls_bf16": _vit_cls(pool_type="gap", cfg=BF16),
+    # distillation: one teacher with labels; two teachers, one on its own input key, mixup, student dropout, no labels
+    "distill_one_teacher_kl": _distill(("prof_a",), cfg=dict(distance="kl"), pool_type="gap"),
+    "distill_two_teachers_mixup_dropout": _distill(
+        ("prof_a", "prof_b"), cfg=dict(mixup=dict(p=0.2, fold_in=None), distance="kl", distance_kw=dict(t=2.0)), rng=7,
+        labels=False, batch=dict(mixup_a=0.75), shapes=dict(prof_b=(4, 48, 48, 3)), pool_type="gap", dropout=0.1),
+    # contrastive trainer: config.loss_fn on the two-tower model, and CLIPPO's one tower
+    "contrastive_softmax": _siglip(_cfg(loss_fn="softmax"), trainer=contrastive),
+    "contrastive_sigmoid": _siglip(_cfg(loss_fn="sigmoid"), trainer=contrastive),
+    "contrastive_chunked_sigmoid": _siglip(_cfg(loss_fn="chunked_sigmoid"), trainer=contrastive),
+    "contrastive_softmax_mb": _siglip(_cfg(loss_fn="softmax", **MB), trainer=contrastive),
+    "clippo_step": _siglip(_cfg(), trainer=contrastive, clippo=True),
+    # GSAM (the scalars it reads back are patched, see _gsam_read_back) and SAM, which runs on a dry run's zeros
+    "gsam_dropout": _vit_cls(trainer=gsam_train, cfg=dict(gsam=GSAM), pool_type="gap", dropout=0.1, rng=7,
+                             read_back=True),
+    "sam": _vit_cls(trainer=gsam_train, cfg=dict(gsam=dict(GSAM, rho_min=0.6, alpha=0.0)), pool_type="gap"),
+    # predict functions
+    "predict_cls_bf16": _vit_cls(pool_type="gap", cfg=BF16, predict=True),
+    "predict_siglip_bf16": _siglip(_cfg(**BF16), predict=True),
+    "predict_distill_student_teacher_ensemble": _distill(("prof_a", "prof_b"), pool_type="gap",
+                                                         predict="student_teacher_ensemble_fwd"),
     # text tower
     "text_last": _text(pool_type="last"),
     "text_first": _text(pool_type="first"),

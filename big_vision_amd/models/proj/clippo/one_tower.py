@@ -24,15 +24,15 @@ The executor is the image half of the two-tower executor (`two_towers.TwoTowersE
 from __future__ import annotations
 
 import importlib
-import math
 
 import torch
 
 from big_vision_amd import engine as E
 from big_vision_amd import ops
-from big_vision_amd import utils
-from big_vision_amd.models.proj.image_text.two_towers import MODELS_PKG, TwoTowersExec
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store, entry_leaf_names, make_store
+from big_vision_amd.models import common
+from big_vision_amd.models.common import MODELS_PKG
+from big_vision_amd.models.proj.image_text.two_towers import TwoTowersExec
+from big_vision_amd.params import ParamStore
 
 F32 = torch.float32
 
@@ -126,8 +126,9 @@ class OneTowerExec(TwoTowersExec):
     self._bwd_img(ctx, halves[0].contiguous() if len(halves) == 1 else torch.cat(halves), sync)
 
 
-class Model:
+class Model(common.Pair):
   """Single ViT to encode regular images and text images."""
+  Exec = OneTowerExec
 
   def __init__(self, image=None, image_model="vit", out_dim=768, temperature_init=10.0, name=None):
     self.image, self.image_model = dict(image or {}), image_model
@@ -135,16 +136,9 @@ class Model:
     self.bias_init = None          # (read by the contrastive trainer: no bias parameter, no sigmoid loss)
     self.image_tower = importlib.import_module(f"{MODELS_PKG}.{image_model}").Model(
         **{"num_classes": out_dim, **self.image}, name="img")
+    self.towers = {"img": self.image_tower}
     self.name = name
     self._execs = {}
-
-  def entries(self, prefix, hw):
-    ents = self.image_tower.entries(f"{prefix}img/", hw)
-    ents.append(Entry(f"{prefix}t", (1,), E.init_const(math.log(self.temperature_init))))
-    return ents
-
-  def scan_prefixes(self, prefix=""):
-    return tuple(getattr(self.image_tower, "scan_prefixes", lambda p: ())(f"{prefix}img/"))
 
   def _geometry(self, image_shape, text_shape):
     """[n, H, W, 3] the tower is laid out for, from whichever input is there (both: they must agree)."""
@@ -156,50 +150,20 @@ class Model:
                        f"got image {image_shape}, text {text_shape}")
     return shapes[0]
 
-  def leaf_names(self, image_shape, text_shape=None):
-    """Leaf names as presented (stacked `encoderblock` for a tower built with scan=True)."""
-    hw = self.image_tower.grid(self._geometry(image_shape, text_shape))
-    return entry_leaf_names(self.entries("", hw), self.scan_prefixes())
-
-  def make_store(self, image_shape, text_shape=None, device=None, frozen_leaves=()):
-    """Allocates the flat parameter store of the tower (+ t).  `frozen_leaves`: see two_towers.Model.make_store."""
-    hw = self.image_tower.grid(self._geometry(image_shape, text_shape))
-    return make_store(self.entries("", hw), device, self.scan_prefixes(), frozen_leaves)
-
-  def init(self, rng, image, text=None, **kw):
-    del kw
-    store = self.make_store(E.input_shape(image), E.input_shape(text))
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
+  def layout(self, image_shape, text_shape=None):
+    return (self.image_tower.layout(self._geometry(image_shape, text_shape)),)
 
   def executor(self, store, prefix, image_shape, text_shape=None):
-    hw = self.image_tower.grid(self._geometry(image_shape, text_shape))
-    key = (id(store), prefix, hw, getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = OneTowerExec(self, store, prefix, hw)
-    return self._execs[key]
+    return self._executor(store, prefix, *self.layout(image_shape, text_shape))
 
   def apply(self, variables, image, text=None, *, train=False, rngs=None, collect=True, **kw):
     """train=True: the tower's dropout (if its config asks for any) is drawn from rngs["dropout"]."""
     del kw
-    drop_key = None
-    if train and float(getattr(self.image_tower, "dropout", 0.0) or 0.0) > 0.0:
-      if not rngs or "dropout" not in rngs:
-        raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-      drop_key = E.seed_of(rngs["dropout"])
+    drop_key = self.dropout_key(train, rngs)
     if text is not None:
       _require_rendered_text(text)
-    params = variables["params"]
     ishape, tshape = E.input_shape(image), E.input_shape(text)
-    if isinstance(params, ParamTree) and params.store is not None:
-      store, prefix = params.store, params.prefix
-    else:
-      geo = self._geometry(ishape, tshape)
-      store = adhoc_store(self._execs, ("one_tower", geo[1:], torch.cuda.current_device()), params,
-                          lambda: self.make_store(geo))
-      prefix = ""
-    store.refresh_shadow()
+    store, prefix = self._store_for(variables["params"], lambda: self.layout(ishape, tshape))
     if image is None and text is None:     # (one_tower.py:53-69: only t is reported)
       t = store.t(f"{prefix}t")
       return None, None, {"t": torch.exp(t), "t/parameter": t}
@@ -208,17 +172,8 @@ class Model:
     return zimg, ztxt, out
 
 
-def _local(source, key):
-  """A checkpoint source of `config.model_init` after the tower's vanity names: remote ones are refused here the way
-  train.load_init refuses them (nothing is fetched)."""
-  if isinstance(source, str) and "://" in source:
-    raise FileNotFoundError(f"config.model_init[{key!r}] resolves to {source!r}: remote checkpoints cannot be opened "
-                            "here; download it and pass the local .npz path")
-  return source
-
-
-# init-file keys of `config.model_init` -> leaf of the param tree (the tower is restored by its own module's load)
-_PARTS = ((("image", "img"), "img"), (("temperature", "t"), "t"))
+# init-file keys of `config.model_init` -> (leaf of the param tree, default tower module or None for a plain array)
+_PARTS = ((("image", "img"), "img", "image_model", "vit"), (("temperature", "t"), "t", None, None))
 
 
 def load(init_params, init_files, model_cfg, img_load_kw={}):  # pylint: disable=dangerous-default-value
@@ -229,20 +184,5 @@ def load(init_params, init_files, model_cfg, img_load_kw={}):  # pylint: disable
   init file keep `init_params`; a key nobody consumed is refused with the reference's message (a typo in a config must
   not pass silently)."""
   todo = {k: f"{init_files}:{k}" for k in ("img", "t")} if isinstance(init_files, str) else dict(init_files)
-  restored_params = dict(init_params) if init_params else {"img": None}
-  for aliases, leaf in _PARTS:
-    found = [todo.pop(a) for a in aliases if a in todo]
-    source = found[0] if found else None
-    if not source:
-      continue
-    if leaf == "t":
-      restored_params[leaf] = utils.load_params(_local(source, aliases[0]))
-    else:
-      tower = importlib.import_module(f"{MODELS_PKG}.{model_cfg.get('image_model', 'vit')}")
-      source = _local(getattr(tower, "VANITY_NAMES", {}).get(source, source), aliases[0])
-      restored_params[leaf] = tower.load(restored_params.get(leaf), source, model_cfg.get("image"), **img_load_kw)
-  init_files = todo
-  assert not init_files, (
-      f"There's something unused left in `config.model_init`. You probably got "
-      f"a typo. Here it is: {init_files}")
-  return restored_params
+  # (a remote source - a tower's vanity name resolves to one - is refused here the way train.load_init refuses it)
+  return common.load_parts(_PARTS, init_params, todo, model_cfg, {"img": img_load_kw}, local_only=True)

@@ -36,8 +36,7 @@ from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import utils
 from big_vision_amd.models import common
-from big_vision_amd.models import vit
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store
+from big_vision_amd.params import Entry, ParamStore
 
 BF16, F32 = torch.bfloat16, torch.float32
 LN_EPS = 1e-12   # flaxformer/architectures/bert: layer norm epsilon of BERT
@@ -120,7 +119,8 @@ class BertExec:
     asynchronously and read by `check_pending()` - which the callers that own a step run BEFORE anything is
     committed: the SigLIP / contrastive trainers right before `opt.step()` (TwoTowersExec.check_inputs: by then the
     copy of this step's first kernels has long completed, and a refused batch leaves the weights untouched),
-    `two_towers.Model.apply` and `Model.apply` of this module before they return (the evaluators' predict_fn) - and,
+    `two_towers.Model.apply` and this tower's own `apply` (common.Tower: late_input_check) before they return (the
+    evaluators' predict_fn) - and,
     as a backstop, when the next batch arrives.  lens is clamped to >= 1 so that a forward that is later refused
     never runs an attention row over zero keys."""
     self.check_pending()
@@ -213,16 +213,15 @@ class BertExec:
         self.seg.grad[0] += dpos.sum(0)
 
 
-class _Model:
-  """BERT encoder with linear projection on the last layer's CLS token (bert.py:33-64)."""
+class _Model(common.Tower):
+  """BERT encoder with linear projection on the last layer's CLS token (bert.py:33-64).  No `encoder`: the blocks are
+  never presented stacked, and two_towers syncs this tower's gradients in one piece."""
+  Exec, late_input_check = BertExec, True
 
   def __init__(self, config, num_classes=None, head_zeroinit=True, name=None):
     self.cfg = dict(CONFIGS[config]) if isinstance(config, str) else dict(config)   # a dict: test-sized encoders
     self.config, self.num_classes, self.head_zeroinit, self.name = config, num_classes, head_zeroinit, name
-    D, H = self.cfg["hidden_size"], self.cfg["num_attention_heads"]
-    if D % H or (D // H) % 8 or D // H > 128:
-      raise NotImplementedError(f"attention kernels need a head_dim that is a multiple of 8 and <= 128, got {D}/{H}")
-    self.depth = 0          # (no `Encoder_0/encoderblock_<i>` ranges: two_towers syncs this tower's gradients in one piece)
+    common.check_head_dim(self.cfg["hidden_size"], self.cfg["num_attention_heads"])
     self._execs = {}
 
   def entries(self, prefix, seq_len):
@@ -242,44 +241,10 @@ class _Model:
       ents += [Entry(f"{P}/mlp_block/mlp/wi/kernel", (D, M), init), Entry(f"{P}/mlp_block/mlp/wi/bias", (M,), E.init_zeros),
                Entry(f"{P}/mlp_block/mlp/wo/kernel", (M, D), init), Entry(f"{P}/mlp_block/mlp/wo/bias", (D,), E.init_zeros)]
       ents += E.ln_entries(f"{P}/mlp_block/layer_norm")(D)
-    if self.num_classes:
-      kinit = E.init_zeros if self.head_zeroinit else E.init_lecun_normal(D)
-      ents += [Entry(f"{prefix}head/kernel", (D, self.num_classes), kinit),
-               Entry(f"{prefix}head/bias", (self.num_classes,), E.init_zeros)]
-    return ents
+    return ents + common.head_entries(prefix, D, self.num_classes, head_zeroinit=self.head_zeroinit)
 
-  def scan_prefixes(self, prefix=""):
-    return ()
-
-  def init(self, rng, text, **kw):
-    del kw
-    dev = text.device if torch.is_tensor(text) and text.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    store = ParamStore(self.entries("", text.shape[1]), dev)
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
-
-  def executor(self, store, prefix, seq_len):
-    key = (id(store), prefix, seq_len, getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = BertExec(self, store, prefix, seq_len)
-    return self._execs[key]
-
-  def apply(self, variables, text, *, train=False, rngs=None, collect=True, **kw):
-    del rngs, train, kw
-    params = variables["params"]
-    if isinstance(params, ParamTree) and params.store is not None:
-      store, prefix = params.store, params.prefix
-    else:
-      dev = torch.device("cuda", torch.cuda.current_device())
-      store = adhoc_store(self._execs, ("bert", int(text.shape[1]), dev.index), params,
-                          lambda: ParamStore(self.entries("", text.shape[1]), dev))
-      prefix = ""
-    store.refresh_shadow()
-    ex = self.executor(store, prefix, text.shape[1])
-    x, out, _ = ex.fwd(text, save=False, collect=collect)
-    ex.check_pending()        # the verdict on THIS batch's input_mask, before its outputs are handed out
-    return x, out
+  def layout(self, text_shape):
+    return text_shape[1]
 
 
 def Model(config, num_classes=None, head_zeroinit=True, **kw):  # pylint: disable=invalid-name

@@ -33,8 +33,9 @@ import torch
 
 from big_vision_amd import engine as E
 from big_vision_amd import ops
+from big_vision_amd.models import common
 from big_vision_amd.models import vit
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store
+from big_vision_amd.params import Entry, ParamStore
 
 F32, BF16 = torch.float32, torch.bfloat16
 
@@ -135,11 +136,8 @@ class NaflexExec:
     ctx.update(pb=pb, W=W, tail=tctx)
     if collect:
       out["encoded"] = t_out["encoded"].view(n, N, D)
-    per_token = (lambda t: t.view(n, N, -1)) if m.pool_type == "none" else (lambda t: t)     # [n, N, .] like the reference's
-    for k in ("head_input", "pre_logits", "logits"):      # (naflex_vit.py:276: head_input is set for every pool_type)
-      if k in t_out:
-        out[k] = per_token(t_out[k])
-    x = per_token(x)
+    x = common.report_tail(out, t_out, x, n, N, per_token=m.pool_type == "none",
+                           keys=("head_input", "pre_logits", "logits"))   # (naflex_vit.py:276: head_input for every pool_type)
     if perm is not None and collect:   # per-token diagnostics back in the caller's token order
       inv = torch.argsort(perm, dim=1)
 
@@ -170,8 +168,9 @@ class NaflexExec:
       self.ln_pre.bwd(dpb, x_in, mean, rstd, T, self.patch_dim)     # only its scale / bias gradients are needed
 
 
-class _Model:
+class _Model(common.Tower):
   """NaFlex ViT (configuration holder + Flax-like init / apply)."""
+  Exec, encoder = NaflexExec, "Transformer"
 
   def __init__(self, num_classes: Optional[int] = None, width: int = 768, depth: int = 12,
                mlp_dim: Optional[int] = None, num_heads: int = 12, rep_size: Union[int, bool] = False,
@@ -188,9 +187,7 @@ class _Model:
       raise NotImplementedError("nposemb > 64")
     if pool_type not in ("map", "gap", "max", "none"):
       raise ValueError(f"Unknown pool type: '{pool_type}'")
-    if width % num_heads or (width // num_heads) % 8 or width // num_heads > 128:
-      raise NotImplementedError(f"attention kernels need a head_dim that is a multiple of 8 and <= 128 (64 is the "
-                                f"fast path), got {width}/{num_heads}")
+    common.check_head_dim(width, num_heads)
     self.num_classes, self.width, self.depth = num_classes, width, depth
     self.mlp_dim, self.num_heads, self.rep_size = mlp_dim or 4 * width, num_heads, rep_size
     self.pool_type, self.head_zeroinit, self.scan = pool_type, head_zeroinit, scan
@@ -213,54 +210,13 @@ class _Model:
     ents += E.encoder_entries(f"{prefix}Transformer", self.depth, D, H, M)
     if self.pool_type == "map":
       ents += E.map_entries(f"{prefix}MAPHead_0", D, H, M)
-    feat = D
-    if self.rep_size:
-      rs = D if self.rep_size is True else self.rep_size
-      ents += [Entry(f"{prefix}pre_logits/kernel", (D, rs), E.init_lecun_normal(D)),
-               Entry(f"{prefix}pre_logits/bias", (rs,), E.init_zeros)]
-      feat = rs
-    if self.num_classes:
-      kinit = E.init_zeros if self.head_zeroinit else E.init_lecun_normal(feat)
-      ents += [Entry(f"{prefix}head/kernel", (feat, self.num_classes), kinit),
-               Entry(f"{prefix}head/bias", (self.num_classes,), E.init_zeros)]
-    return ents
+    return ents + common.head_entries(prefix, D, self.num_classes, self.rep_size, self.head_zeroinit)
 
-  def grid(self, image_shape):
-    """two_towers asks the image tower for its 'grid'; for NaFlex the layout key is the patch dimension."""
-    return int(image_shape[-1])
+  def layout(self, patches_shape):
+    """The patches arrive flattened (naflex_vit.py:227): what the parameters depend on is the patch dimension."""
+    return int(patches_shape[-1])
 
-  def scan_prefixes(self, prefix=""):
-    return (f"{prefix}Transformer",) if self.scan else ()
-
-  def init(self, rng, image, **kw):
-    del kw
-    patches = image[0]
-    dev = patches.device if torch.is_tensor(patches) and patches.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    store = ParamStore(self.entries("", int(patches.shape[-1])), dev, scan_prefixes=self.scan_prefixes())
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
-
-  def executor(self, store, prefix, patch_dim):
-    key = (id(store), prefix, int(patch_dim), getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = NaflexExec(self, store, prefix, int(patch_dim))
-    return self._execs[key]
-
-  def apply(self, variables, image, *, train=False, rngs=None, collect=True, **kw):
-    del rngs, train, kw
-    pd = int(image[0].shape[-1])
-    params = variables["params"]
-    if isinstance(params, ParamTree) and params.store is not None:
-      store, prefix = params.store, params.prefix
-    else:
-      dev = torch.device("cuda", torch.cuda.current_device())
-      store = adhoc_store(self._execs, ("naflex", pd, dev.index), params,
-                          lambda: ParamStore(self.entries("", pd), dev, scan_prefixes=self.scan_prefixes()))
-      prefix = ""
-    store.refresh_shadow()
-    x, out, _ = self.executor(store, prefix, pd).fwd(image, save=False, collect=collect)
-    return x, out
+  grid = layout     # (the name callers that treat this tower like the pixel-input ViT know it by)
 
 
 def Model(num_classes=None, *, variant=None, **kw):  # pylint: disable=invalid-name

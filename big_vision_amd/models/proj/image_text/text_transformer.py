@@ -17,7 +17,7 @@ from big_vision_amd import ops
 from big_vision_amd import utils
 from big_vision_amd.models import common
 from big_vision_amd.models import vit
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store
+from big_vision_amd.params import Entry, ParamStore
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -71,8 +71,9 @@ class TextExec:
       ops.batchsum(dx0, self.pos.grad, n, L, D)
 
 
-class _Model:
+class _Model(common.Tower):
   """Text transformer similar to CLIP (config holder + Flax-like init/apply)."""
+  Exec, encoder = TextExec, "Encoder_0"
 
   def __init__(self, num_classes, width=512, depth=12, mlp_dim=2048, num_heads=8, dropout=0.0,
                vocab_size=32_000, pool_type="last", scan=False, remat_policy="nothing_saveable",
@@ -82,9 +83,7 @@ class _Model:
     self.dropout = float(dropout)
     if pool_type not in ("last", "first", "mean", "gap", "max", "gmp", "map"):
       raise NotImplementedError(f"Cannot do pooling '{pool_type}'")
-    if width % num_heads or (width // num_heads) % 8 or width // num_heads > 128:
-      raise NotImplementedError(f"attention kernels need a head_dim that is a multiple of 8 and <= 128 (64 is the "
-                                f"fast path), got {width}/{num_heads}")
+    common.check_head_dim(width, num_heads)
     self.num_classes, self.width, self.depth, self.mlp_dim = num_classes, width, depth, mlp_dim
     self.num_heads, self.vocab_size, self.pool_type, self.scan = num_heads, vocab_size, pool_type, scan
     self.name = name
@@ -98,44 +97,10 @@ class _Model:
     ents += E.encoder_entries(f"{prefix}Encoder_0", self.depth, D, H, M)
     if self.pool_type == "map":
       ents += E.map_entries(f"{prefix}MAPHead_0", D, H, M)
-    if self.num_classes:
-      ents += [Entry(f"{prefix}head/kernel", (D, self.num_classes), E.init_lecun_normal(D)),
-               Entry(f"{prefix}head/bias", (self.num_classes,), E.init_zeros)]
-    return ents
+    return ents + common.head_entries(prefix, D, self.num_classes, head_zeroinit=False)
 
-  def scan_prefixes(self, prefix=""):
-    """Encoders presented with stacked blocks (scan=True)."""
-    return (f"{prefix}Encoder_0",) if self.scan else ()
-
-  def init(self, rng, text, **kw):
-    del kw
-    dev = text.device if torch.is_tensor(text) and text.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    store = ParamStore(self.entries("", text.shape[1]), dev, scan_prefixes=self.scan_prefixes())
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
-
-  def executor(self, store, prefix, seq_len):
-    key = (id(store), prefix, seq_len, getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = TextExec(self, store, prefix, seq_len)
-    return self._execs[key]
-
-  def apply(self, variables, text, *, train=False, rngs=None, collect=True, **kw):
-    del kw
-    params = variables["params"]
-    if isinstance(params, ParamTree) and params.store is not None:
-      store, prefix = params.store, params.prefix
-    else:
-      dev = torch.device("cuda", torch.cuda.current_device())
-      store = adhoc_store(self._execs, ("txt", int(text.shape[1]), dev.index), params,
-                          lambda: ParamStore(self.entries("", text.shape[1]), dev,
-                                             scan_prefixes=self.scan_prefixes()))
-      prefix = ""
-    store.refresh_shadow()
-    x, out, _ = self.executor(store, prefix, text.shape[1]).fwd(text, save=False, collect=collect,
-                                                                drop=vit.dropout_for(self.dropout, train, rngs))
-    return x, out
+  def layout(self, text_shape):
+    return text_shape[1]
 
 
 def Model(num_classes, *, variant=None, **kw):  # pylint: disable=invalid-name

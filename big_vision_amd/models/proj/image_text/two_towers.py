@@ -17,11 +17,11 @@ import torch
 
 from big_vision_amd import engine as E
 from big_vision_amd import ops
-from big_vision_amd import utils
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store, entry_leaf_names, make_store
+from big_vision_amd.models import common
+from big_vision_amd.models.common import MODELS_PKG
+from big_vision_amd.params import ParamStore
 
 F32 = torch.float32
-MODELS_PKG = "big_vision_amd.models"
 
 
 _SIDE_STREAMS = {}
@@ -165,18 +165,18 @@ class TwoTowersExec:
       if chk is not None:
         chk()
 
-  def _block_ranges(self, tower, enc):
-    """{block index: [lo, hi) of its gradients in the flat buffer} for `tower` ('img/' | 'txt/')."""
-    key = (tower, enc)
-    if key not in self._ranges:
-      tw = self.m.image_tower if tower.endswith("img/") else self.m.text_tower
+  def _block_ranges(self, tower):
+    """{block index: [lo, hi) of its gradients in the flat buffer} for `tower` ('img' | 'txt'); empty for a tower
+    without an `<encoder>/encoderblock_<i>` sequence (BERT: its gradients are synced in one piece)."""
+    if tower not in self._ranges:
+      tw = self.m.towers[tower]
       out = {}
-      for i in range(getattr(tw, "depth", 0)):
-        r = self.store.grad_range(lambda n, p=f"{tower}{enc}/encoderblock_{i}/": n.startswith(p))
+      for i in range(tw.depth if tw.encoder else 0):
+        r = self.store.grad_range(lambda n, p=f"{self.prefix}{tower}/{tw.encoder}/encoderblock_{i}/": n.startswith(p))
         if r is not None:
           out[i] = r
-      self._ranges[key] = out
-    return self._ranges[key]
+      self._ranges[tower] = out
+    return self._ranges[tower]
 
   def bwd(self, ctx, dzimg, dztxt, sync=None):
     """dzimg / dztxt: gradients w.r.t. the NORMALISED embeddings (None = tower skipped).
@@ -211,7 +211,7 @@ class TwoTowersExec:
     c, z, norm = ctx["txt"]
     on_block = None
     if sync is not None:
-      rt = self._block_ranges(f"{self.prefix}txt/", "Encoder_0")
+      rt = self._block_ranges("txt")
       on_block = lambda i, rt=rt: sync.launch(*rt[i]) if i in rt else None
     self.txt.bwd(c, ops.l2norm_bwd(z, norm, dztxt), on_block=on_block)
     if sync is not None:
@@ -224,7 +224,7 @@ class TwoTowersExec:
     c, z, norm = ctx["img"]
     on_block = None
     if sync is not None:
-      ri = self._block_ranges(f"{self.prefix}img/", "Transformer")
+      ri = self._block_ranges("img")
       stem = tuple(f"{self.prefix}img/{k}" for k in ("embedding", "pos_embedding", "cls", "patchln_pre", "patchln_post"))
       tail = store.grad_range(lambda n: n.startswith(f"{self.prefix}img/") and "/encoderblock_" not in n
                               and not n.startswith(stem))
@@ -238,8 +238,9 @@ class TwoTowersExec:
     self.img.bwd(c, ops.l2norm_bwd(z, norm, dzimg), on_block=on_block)
 
 
-class Model:
+class Model(common.Pair):
   """Two towers transformer."""
+  Exec = TwoTowersExec
 
   def __init__(self, image=None, text=None, text_model="proj.image_text.text_transformer",
                image_model="vit", out_dim=128, temperature_init=1.0, bias_init=None, name=None):
@@ -251,46 +252,17 @@ class Model:
         **{"num_classes": out_dims[1], **self.text}, name="txt")
     self.image_tower = importlib.import_module(f"{MODELS_PKG}.{image_model}").Model(
         **{"num_classes": out_dims[0], **self.image}, name="img")
+    self.towers = {"img": self.image_tower, "txt": self.text_tower}
     self._execs = {}
 
-  def entries(self, prefix, hw, seq_len):
-    ents = self.image_tower.entries(f"{prefix}img/", hw) + self.text_tower.entries(f"{prefix}txt/", seq_len)
-    ents.append(Entry(f"{prefix}t", (1,), E.init_const(math.log(self.temperature_init))))
-    if self.bias_init is not None:
-      ents.append(Entry(f"{prefix}b", (1,), E.init_const(self.bias_init)))
-    return ents
-
-  def scan_prefixes(self, prefix=""):
-    sp = getattr(self.image_tower, "scan_prefixes", lambda p: ())(f"{prefix}img/")
-    return tuple(sp) + tuple(getattr(self.text_tower, "scan_prefixes", lambda p: ())(f"{prefix}txt/"))
-
-  def leaf_names(self, image_shape, text_shape):
-    """Leaf names as presented (stacked `encoderblock` for towers built with scan=True)."""
-    hw = self.image_tower.grid(tuple(image_shape))
-    return entry_leaf_names(self.entries("", hw, text_shape[1]), self.scan_prefixes())
-
-  def make_store(self, image_shape, text_shape, device=None, frozen_leaves=()):
-    """Allocates the flat parameter store for both towers (+ t, b).
-
-    `frozen_leaves`: exact Flax leaf names that get no gradient / optimizer
-    state (config.schedule None entries); they are laid out last (params.make_store)."""
-    hw = self.image_tower.grid(tuple(image_shape))
-    return make_store(self.entries("", hw, text_shape[1]), device, self.scan_prefixes(), frozen_leaves)
-
-  def init(self, rng, image, text=None, **kw):
-    del kw
-    store = self.make_store(E.input_shape(image), tuple(text.shape))
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
+  def layout(self, image_shape, text_shape):
+    return self.image_tower.layout(tuple(image_shape)), self.text_tower.layout(tuple(text_shape))
 
   def executor(self, store, prefix, image_shape, text_shape):
-    hw = self.image_tower.grid(tuple(image_shape)) if image_shape is not None else None
-    sl = text_shape[1] if text_shape is not None else None
-    key = (id(store), prefix, hw, sl, getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = TwoTowersExec(self, store, prefix, hw, sl)
-    return self._execs[key]
+    """(an absent input's shape is None: that tower gets no executor)"""
+    hw = self.image_tower.layout(tuple(image_shape)) if image_shape is not None else None
+    sl = self.text_tower.layout(tuple(text_shape)) if text_shape is not None else None
+    return self._executor(store, prefix, hw, sl)
 
   def _image_shape_of(self, params):
     """(1, H, W, 3) of the images an ad-hoc parameter tree was built for, from its learned position embedding (a
@@ -308,23 +280,13 @@ class Model:
   def apply(self, variables, image, text=None, *, train=False, rngs=None, collect=True, **kw):
     """train=True: the towers' dropout (if their configs ask for any) is drawn from rngs["dropout"] (siglip.py:288-290)."""
     del kw
-    drop_key = None
-    if train and any(float(getattr(t, "dropout", 0.0) or 0.0) > 0.0 for t in (self.image_tower, self.text_tower)):
-      if not rngs or "dropout" not in rngs:
-        raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-      drop_key = E.seed_of(rngs["dropout"])
+    drop_key = self.dropout_key(train, rngs)
     params = variables["params"]
-    if isinstance(params, ParamTree) and params.store is not None:
-      store, prefix = params.store, params.prefix
-    else:
-      # two_towers.py:43: either input may be None.  The store holds BOTH towers' parameters, so the geometry of the
-      # absent input is read off the tree itself (position-embedding lengths)
-      ishape = E.input_shape(image) or self._image_shape_of(params)
-      tshape = tuple(text.shape) if text is not None else (1, int(params["txt"]["pos_embedding"].shape[1]))
-      store = adhoc_store(self._execs, ("two_towers", ishape[1:], tshape[1:], torch.cuda.current_device()),
-                          params, lambda: self.make_store(ishape, tshape))
-      prefix = ""
-    store.refresh_shadow()
+    # two_towers.py:43: either input may be None.  The store holds BOTH towers' parameters, so for a plain tree the
+    # geometry of the absent input is read off the tree itself (position-embedding lengths)
+    store, prefix = self._store_for(params, lambda: self.layout(
+        E.input_shape(image) or self._image_shape_of(params),
+        tuple(text.shape) if text is not None else (1, int(params["txt"]["pos_embedding"].shape[1]))))
     ex = self.executor(store, prefix, E.input_shape(image), E.input_shape(text))
     zimg, ztxt, out, _ = ex.fwd(image, text, save=False, collect=collect, drop_key=drop_key)
     ex.check_inputs()
@@ -354,23 +316,7 @@ def load(init_params, init_files, model_cfg, img_load_kw={}, txt_load_kw={}):  #
     todo = {k: f"{init_files}:{k}" for k in parts}
   else:
     todo = dict(init_files)
-  restored_params = dict(init_params) if init_params else {"img": None, "txt": None}
-  tower_kw = {"img": img_load_kw, "txt": txt_load_kw}
-  for aliases, leaf, module_key, default_module in _PARTS:
-    found = [todo.pop(a) for a in aliases if a in todo]
-    source = found[0] if found else None
-    if not source:
-      continue
-    if module_key is None:
-      restored_params[leaf] = utils.load_params(source)
-    else:
-      tower = importlib.import_module(f"{MODELS_PKG}.{model_cfg.get(module_key, default_module)}")
-      restored_params[leaf] = tower.load(restored_params.get(leaf), source, model_cfg.get(aliases[0]), **tower_kw[leaf])
-  init_files = todo
-  assert not init_files, (
-      f"There's something unused left in `config.model_init`. You probably got "
-      f"a typo. Here it is: {init_files}")
-  return restored_params
+  return common.load_parts(_PARTS, init_params, todo, model_cfg, {"img": img_load_kw, "txt": txt_load_kw})
 
 
 # Shortcut names for some canonical paper checkpoints (gs:// paths; kept for

@@ -19,7 +19,7 @@ from big_vision_amd import engine as E
 from big_vision_amd import ops
 from big_vision_amd import utils
 from big_vision_amd.models import common
-from big_vision_amd.params import Entry, ParamStore, ParamTree, adhoc_store
+from big_vision_amd.params import Entry, ParamStore
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -56,14 +56,7 @@ def decode_variant(variant):
 _seed_of = E.seed_of      # (its home is engine.py, next to Dropout; the name stays for the tests that use it)
 
 
-def dropout_for(rate, train, rngs):
-  """engine.Dropout of an `apply(..., train=, rngs=)` call, None when the call is deterministic (flax: a module with
-  dropout > 0 applied with train=True and no "dropout" rng raises)."""
-  if not train or not rate:
-    return None
-  if not rngs or "dropout" not in rngs:
-    raise ValueError("train=True with dropout > 0 needs rngs={'dropout': key}")
-  return E.Dropout(rate, E.seed_of(rngs["dropout"]))
+dropout_for = common.dropout_for
 
 
 class VitExec:
@@ -126,13 +119,9 @@ class VitExec:
     ctx = dict(n=n, L=L, L0=L0, patches=patches, tail=tctx, k_pos=k_pos)
     if collect:
       out["encoded"] = t_out["encoded"].view(n, L, D)   # all L (+1 cls) tokens, as in the reference (vit.py:240); x_2d drops the cls row
-    per_token = (lambda t: t.view(n, L, -1)) if m.pool_type == "none" else (lambda t: t)   # like the reference's un-pooled x
     if m.pool_type != "none":
       out["head_input"] = t_out["head_input"]
-    for k in ("pre_logits", "logits"):
-      if k in t_out:
-        out[k] = per_token(t_out[k])
-    x = per_token(x)
+    x = common.report_tail(out, t_out, x, n, L, per_token=m.pool_type == "none")
     pre, head = self.tail.pre, self.tail.head
     if collect and "encoded" in out:
       # the same tail applied to every patch token (vit.py:257-273: x_2d; unused by training)
@@ -161,7 +150,7 @@ class VitExec:
       ops.batchsum(dx0, self.pos.grad, n, L0, D)
 
 
-class _Model:
+class _Model(common.Tower):
   """ViT model (configuration holder + Flax-like init/apply).
 
   Two reference arguments are accepted for config compatibility and have no effect here, by design:
@@ -172,6 +161,7 @@ class _Model:
   what `float32` + XLA's default TPU matmul precision amounts to; parameters, residual stream,
   LayerNorm, softmax and the loss stay fp32 in both.
   """
+  Exec, encoder = VitExec, "Transformer"
 
   def __init__(self, num_classes: Optional[int] = None, patch_size: Sequence[int] = (16, 16),
                width: int = 768, depth: int = 12, mlp_dim: Optional[int] = None, num_heads: int = 12,
@@ -185,9 +175,7 @@ class _Model:
     if not 0.0 <= float(dropout) < 1.0:
       raise ValueError(f"dropout must be in [0, 1), got {dropout}")
     self.dropout = float(dropout)
-    if width % num_heads or (width // num_heads) % 8 or width // num_heads > 128:
-      raise NotImplementedError(f"attention kernels need a head_dim that is a multiple of 8 and <= 128 (64 is the "
-                                f"fast path), got {width}/{num_heads}")
+    common.check_head_dim(width, num_heads)
     self.num_classes, self.patch_size = num_classes, tuple(patch_size)
     self.width, self.depth, self.mlp_dim = width, depth, mlp_dim or 4 * width
     self.num_heads, self.posemb, self.rep_size = num_heads, posemb, rep_size
@@ -208,56 +196,10 @@ class _Model:
     ents += E.encoder_entries(f"{prefix}Transformer", self.depth, D, H, M)
     if self.pool_type == "map":
       ents += E.map_entries(f"{prefix}MAPHead_0", D, H, M)
-    feat = D
-    if self.rep_size:
-      rs = D if self.rep_size is True else self.rep_size
-      ents += [Entry(f"{prefix}pre_logits/kernel", (D, rs), E.init_lecun_normal(D)),
-               Entry(f"{prefix}pre_logits/bias", (rs,), E.init_zeros)]
-      feat = rs
-    if self.num_classes:
-      kinit = E.init_zeros if self.head_zeroinit else E.init_lecun_normal(feat)
-      ents += [Entry(f"{prefix}head/kernel", (feat, self.num_classes), kinit),
-               Entry(f"{prefix}head/bias", (self.num_classes,), E.init_zeros)]
-    return ents
+    return ents + common.head_entries(prefix, D, self.num_classes, self.rep_size, self.head_zeroinit)
 
   def grid(self, image_shape):
     return (image_shape[1] // self.patch_size[0], image_shape[2] // self.patch_size[1])
-
-  def scan_prefixes(self, prefix=""):
-    """Encoders presented with stacked blocks (scan=True, vit.py:129-148)."""
-    return (f"{prefix}Transformer",) if self.scan else ()
-
-  def init(self, rng, image, **kw):
-    del kw
-    shape = tuple(image.shape)
-    dev = image.device if torch.is_tensor(image) and image.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    store = ParamStore(self.entries("", self.grid(shape)), dev, scan_prefixes=self.scan_prefixes())
-    store.init_random(E.seed_of(rng))
-    store.refresh_shadow()
-    return {"params": store.tree()}
-
-  def executor(self, store, prefix, hw):
-    key = (id(store), prefix, tuple(hw), getattr(store, "want_grads", False))
-    if key not in self._execs:
-      self._execs[key] = VitExec(self, store, prefix, hw)
-    return self._execs[key]
-
-  def _store_for(self, params, hw):
-    if isinstance(params, ParamTree) and params.store is not None:
-      return params.store, params.prefix
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return adhoc_store(self._execs, ("vit", tuple(hw), dev.index), params,
-                       lambda: ParamStore(self.entries("", hw), dev, scan_prefixes=self.scan_prefixes())), ""
-
-  def apply(self, variables, image, *, train=False, rngs=None, collect=True, **kw):
-    """train=True with dropout > 0 needs rngs={"dropout": key} (vit.py:228, train.py:298), as in the reference."""
-    del kw
-    hw = self.grid(tuple(image.shape))
-    store, prefix = self._store_for(variables["params"], hw)
-    store.refresh_shadow()
-    x, out, _ = self.executor(store, prefix, hw).fwd(image, save=False, collect=collect,
-                                                     drop=dropout_for(self.dropout, train, rngs))
-    return x, out
 
   __call__ = None  # Flax-style direct calls are not supported; use .apply
 

@@ -36,7 +36,7 @@ from big_vision_amd import ops
 from big_vision_amd import optax as bv_optax
 from big_vision_amd import sharding
 from big_vision_amd import utils as u
-from big_vision_amd.params import entry_leaf_names, make_store
+from big_vision_amd.models import common
 
 F32 = torch.float32
 LOSSES = {"softmax_xent": ops.softmax_xent, "sigmoid_xent": ops.sigmoid_xent}
@@ -59,8 +59,7 @@ def _loss_kernel(config):
 def make_train_state(model, config, image_shape, *, rng=0, comm=None, total_steps=None, device=None, after_init=None):
   """Parameter store + optimizer laid out for `config` (replaces train.py:191-262).  after_init(store): edits of the
   random init that a checkpoint load may still overwrite (a trainer's `init_head_bias`)."""
-  ents, sp = model.entries("", model.grid(tuple(image_shape))), model.scan_prefixes()
-  store = make_store(ents, device, sp, bv_optax.frozen_leaves(config, entry_leaf_names(ents, sp)))
+  store = model.make_store(image_shape, device, bv_optax.frozen_leaves(config, model.leaf_names(image_shape)))
   store.init_random(E.seed_of(rng))
   if after_init is not None:
     after_init(store)
@@ -101,9 +100,7 @@ def load_init(model, store, init, model_cfg, load_kw, key):
   if not hasattr(model_mod, "load"):
     raise NotImplementedError(f"config.{key}: {model_mod.__name__} has no load()")
   path = getattr(model_mod, "VANITY_NAMES", {}).get(init, init) if isinstance(init, str) else init
-  if isinstance(path, str) and "://" in path:
-    raise FileNotFoundError(f"config.{key}={init!r} resolves to {path!r}: remote checkpoints cannot be opened "
-                            "here; download it and pass the local .npz path")
+  common.refuse_remote(path, f"config.{key}={init!r}")
   if isinstance(path, str) and not any(os.path.isfile(p) for p in (path, path.rsplit(":", 1)[0])):
     raise FileNotFoundError(f"config.{key}={init!r}: no such checkpoint file (remote vanity names are not "
                             "fetched; pass the local .npz path)")

@@ -33,7 +33,6 @@ from big_vision_amd import ops
 from big_vision_amd import optax as bv_optax
 from big_vision_amd import train as bv_train
 from big_vision_amd import utils as u
-from big_vision_amd.params import entry_leaf_names, make_store
 
 F32 = torch.float32
 
@@ -69,8 +68,7 @@ def make_train_state(models, config, image_shapes, *, rng=0, comm=None, total_st
   # -- student
   model = models["student"]
   shape = _image_shape(image_shapes, "student")
-  ents, sp = model.entries("", model.grid(shape)), model.scan_prefixes()
-  store = make_store(ents, device, sp, bv_optax.frozen_leaves(config, entry_leaf_names(ents, sp)))
+  store = model.make_store(shape, device, bv_optax.frozen_leaves(config, model.leaf_names(shape)))
   store.init_random(seed)
   if "init_head_bias" in config:
     store.leaf("head/bias").fill_(float(config["init_head_bias"]))
@@ -84,8 +82,7 @@ def make_train_state(models, config, image_shapes, *, rng=0, comm=None, total_st
   # -- teachers: never optimised, never checkpointed
   for i, name in enumerate(config.teachers):
     m = models[name]
-    hw = m.grid(_image_shape(image_shapes, name))
-    ts = make_store(m.entries("", hw), device, m.scan_prefixes())
+    ts = m.make_store(_image_shape(image_shapes, name), device)
     ts.init_random(seed + 1 + i)
     bv_train.load_init(m, ts, config[f"{name}_init"], config.get(name), config.get(f"{name}_load", {}),
                        key=f"{name}_init")

@@ -33,8 +33,9 @@ from big_vision_amd import utils as u  # noqa: E402
 from big_vision_amd.compat.ml_collections import ConfigDict  # noqa: E402
 from big_vision_amd.models import vit  # noqa: E402
 from big_vision_amd.models.proj.clippo import one_tower  # noqa: E402
+from big_vision_amd.models.proj.flaxformer import bert  # noqa: E402
 from big_vision_amd.models.proj.image_text import naflex_vit, text_transformer, two_towers  # noqa: E402
-from big_vision_amd.params import ParamStore  # noqa: E402
+from big_vision_amd.params import ParamStore, flatten_tree  # noqa: E402
 from big_vision_amd.trainers.proj.distill import distill  # noqa: E402
 from big_vision_amd.trainers.proj.gsam import train as gsam_train  # noqa: E402
 from big_vision_amd.trainers.proj.image_text import contrastive, siglip  # noqa: E402
@@ -208,13 +209,68 @@ def _distill(teachers, cfg=None, rng=0, labels=True, batch=None, shapes=None, pr
   return case
 
 
+@contextlib.contextmanager
+def _cpu_for_cuda():
+  """An ad-hoc `apply` allocates its store on the current GPU: the dry run's is the CPU."""
+  cpu = torch.empty(0).device
+  with mock.patch.object(torch, "device", lambda *a, **k: cpu), mock.patch.object(torch.cuda, "current_device", lambda: 0):
+    yield
+
+
+def _plain(store):
+  """The store's values as a plain numpy tree, bound to no store (what a checkpoint reader hands to `apply`)."""
+  return u.tree_map(lambda v: v.numpy().copy(), dict(store.tree()))
+
+
+def _apply_adhoc(m, tree, *inputs):
+  with _cpu_for_cuda():
+    return m.apply({"params": tree}, *inputs, collect=True)
+
+
+def _tower_setup(make_model, key, inputs, scan=False):
+  """(model, its initialised CPU store, the inputs of `apply`) of ONE tower."""
+  m = make_model()
+  store = ParamStore(m.entries("", key), "cpu", scan_prefixes=m.scan_prefixes() if scan else ())
+  store.init_random(0)
+  store.refresh_shadow()
+  return m, store, (inputs,)
+
+
+def _pair_setup(clippo=False, image=True, text=True):
+  """(model, its initialised CPU store, the inputs of `apply`) of a pair model; an absent input is None."""
+  if clippo:
+    model = one_tower.Model(image=IMG, out_dim=64)
+  else:
+    model = two_towers.Model(image=IMG, text=TXT, out_dim=(None, 64), temperature_init=10.0, bias_init=-10.0)
+  images = torch.zeros((2, 32, 32, 3))
+  labels = torch.zeros((2, 32, 32, 3)) if clippo else torch.ones((2, 8), dtype=torch.int32)
+  store = model.make_store(tuple(images.shape), tuple(labels.shape), device="cpu")
+  store.init_random(0)
+  store.refresh_shadow()
+  return model, store, (images if image else None, labels if text else None)
+
+
+def _apply(setup, adhoc=False, then_no_input=False):
+  """`model.apply(..., collect=True)` on a tree bound to its store, or (adhoc) on a plain numpy tree;
+  then_no_input: followed by the store-bound apply without any input (one_tower reports `t` alone)."""
+  def case():
+    m, store, inputs = setup()
+    if adhoc:
+      tree = _plain(store)
+      return lambda: _apply_adhoc(m, tree, *inputs)
+
+    def run():
+      m.apply({"params": store.tree()}, *inputs, collect=True)
+      if then_no_input:
+        m.apply({"params": store.tree()}, None, None)
+    return run
+  return case
+
+
 def _tower(make_model, key, inputs, collect=False, scan=False):
   """Forward + backward of ONE tower through its executor (collect: `model.apply(..., collect=True)` instead)."""
   def case():
-    m = make_model()
-    store = ParamStore(m.entries("", key), "cpu", scan_prefixes=m.scan_prefixes() if scan else ())
-    store.init_random(0)
-    store.refresh_shadow()
+    m, store, _ = _tower_setup(make_model, key, inputs, scan)
     if collect:
       return lambda: m.apply({"params": store.tree()}, inputs, collect=True)
     store.want_grads = True
@@ -231,6 +287,20 @@ def _tower(make_model, key, inputs, collect=False, scan=False):
 def _text(collect=False, scan=False, **kw):
   ids = torch.ones((2, 8), dtype=torch.int32)
   return _tower(lambda: text_transformer.Model(64, **TINY, vocab_size=50, scan=scan, **kw), 8, ids, collect, scan)
+
+
+def _text_setup():
+  return _tower_setup(lambda: text_transformer.Model(64, **TINY, vocab_size=50), 8, torch.ones((2, 8), dtype=torch.int32))
+
+
+def _bert_setup():
+  return _tower_setup(lambda: bert.Model(BERT, num_classes=64), 8, torch.ones((2, 8), dtype=torch.int32))
+
+
+def _naflex_setup():
+  batch = _naflex_batch()
+  return _tower_setup(lambda: naflex_vit.Model(16, **TINY, nposemb=4, posemb="learn_2d(16)"), int(batch[0].shape[-1]),
+                      batch)
 
 
 def _naflex_batch(holes=False):
@@ -336,7 +406,20 @@ CASES = {
     "naflex_apply_collect_map": _naflex(pool_type="map", collect=True),
     "text_apply_collect_last": _text(pool_type="last", collect=True),
     "text_apply_collect_map": _text(pool_type="map", collect=True),
+    "bert_apply_collect": _apply(_bert_setup),
+    "one_tower_apply_collect_then_no_input": _apply(lambda: _pair_setup(clippo=True), then_no_input=True),
+    # model.apply on a plain numpy tree: the ad-hoc store of the geometry, re-loaded from the tree
+    "text_apply_adhoc": _apply(_text_setup, adhoc=True),
+    "naflex_apply_adhoc": _apply(_naflex_setup, adhoc=True),
+    "bert_apply_adhoc": _apply(_bert_setup, adhoc=True),
+    "two_towers_apply_adhoc_no_text": _apply(lambda: _pair_setup(text=False), adhoc=True),
+    "two_towers_apply_adhoc_no_image": _apply(lambda: _pair_setup(image=False), adhoc=True),
+    "one_tower_apply_adhoc": _apply(lambda: _pair_setup(clippo=True), adhoc=True),
 }
+
+ADHOC = {"text": _text_setup, "naflex": _naflex_setup, "bert": _bert_setup,
+         "two_towers_no_text": lambda: _pair_setup(text=False), "two_towers_no_image": lambda: _pair_setup(image=False),
+         "one_tower": lambda: _pair_setup(clippo=True)}
 
 
 TABLE = os.path.join(GOLDEN, "_launches.json")      # every distinct launch of all cases, one per line
@@ -360,9 +443,13 @@ def _golden(name):
 
 
 def _write_goldens():
-  """Table in order of first appearance over the sorted cases; index lists wrapped at 40 numbers a line."""
+  """The table keeps the lines it has (a new case leaves the goldens of the others as they are) and grows at its end, in
+  order of first appearance over the sorted cases; index lists wrapped at 40 numbers a line."""
   os.makedirs(GOLDEN, exist_ok=True)
   index = {}
+  if os.path.exists(TABLE):
+    with open(TABLE) as f:
+      index = {_key(launch): i for i, launch in enumerate(json.load(f))}
   for name in sorted(CASES):
     trace = record(CASES[name])
     order = [index.setdefault(_key(launch), len(index)) for launch in trace]
@@ -399,6 +486,42 @@ def test_a_recording_is_a_function_of_the_code_alone():
   a, b = record(CASES["siglip_single"]), record(CASES["siglip_single"])
   assert a == b
   assert sum(launch[0] == "bv_ctx_set_workspace" for launch in a) == 1
+
+
+@pytest.mark.parametrize("name", sorted(ADHOC))
+def test_adhoc_apply_reloads_the_tree_every_call(name):
+  """What tests/test_advice_r1_cpu.py asserts for the ViT, for every other model: two different plain trees and an
+  in-place edit of one each reach the device store, and only one store per geometry is kept."""
+  with dry_run([]):
+    m, ref, inputs = ADHOC[name]()
+    tree_a = _plain(ref)
+    tree_b = u.tree_map(lambda v: v + 1.0, tree_a)
+    _apply_adhoc(m, tree_a, *inputs)
+    stores = [v for k, v in m._execs.items() if k[0] == "adhoc"]
+    assert len(stores) == 1
+    st = stores[0]
+    for leaf, want in flatten_tree(tree_a).items():
+      assert torch.equal(st.leaf(leaf), torch.from_numpy(want)), leaf
+    _apply_adhoc(m, tree_b, *inputs)
+    flat_b = flatten_tree(tree_b)
+    for leaf, want in flat_b.items():
+      assert torch.equal(st.leaf(leaf), torch.from_numpy(want)), leaf
+    leaf = sorted(flat_b)[-1]
+    flat_b[leaf][...] = 7.0
+    _apply_adhoc(m, tree_b, *inputs)
+    assert bool((st.leaf(leaf) == 7.0).all())
+    assert len([k for k in m._execs if k[0] == "adhoc"]) == 1
+  ops._contexts.clear()
+
+
+def test_one_tower_apply_without_inputs_reports_only_t():
+  """one_tower.py:53-69: neither an image nor a text - no embeddings, `out` holds the temperature alone."""
+  with dry_run([]):
+    m, store, _ = _pair_setup(clippo=True)
+    zimg, ztxt, out = m.apply({"params": store.tree()}, None, None)
+  ops._contexts.clear()
+  assert zimg is None and ztxt is None and sorted(out) == ["t", "t/parameter"]
+  assert torch.equal(out["t/parameter"], store.leaf("t")) and torch.equal(out["t"], torch.exp(store.leaf("t")))
 
 
 if __name__ == "__main__":

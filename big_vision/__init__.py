@@ -31,6 +31,10 @@ class _AliasLoader(importlib.abc.Loader):
   def exec_module(self, module):
     pass                                             # already executed under its own name
 
+  def get_code(self, fullname):
+    """`python -m big_vision.tools.eval_only` (runpy) runs the implementation's code as `__main__`."""
+    return importlib.util.find_spec(self.target).loader.get_code(self.target)
+
 
 class _AliasFinder(importlib.abc.MetaPathFinder):
   def find_spec(self, fullname, path=None, target=None):
@@ -45,7 +49,8 @@ class _AliasFinder(importlib.abc.MetaPathFinder):
       raise ModuleNotFoundError(
           f"No module named '{fullname}': '{real}' does not exist - this part of big_vision is outside "
           "the accelerated hot path (SURVEY.md §8)", name=fullname)
-    spec = importlib.util.spec_from_loader(fullname, _AliasLoader(real), is_package=found.submodule_search_locations is not None)
+    spec = importlib.util.spec_from_loader(fullname, _AliasLoader(real), origin=found.origin,
+                                           is_package=found.submodule_search_locations is not None)
     return spec
 
 

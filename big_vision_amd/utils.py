@@ -249,9 +249,11 @@ def _to_numpy(v):
   return np.asarray(v)
 
 
-def save_params_npz(fname, tree):
+def save_params_npz(fname, tree, compressed=False):
+  """`tree` as a flat .npz under '/'-joined names, what `load_checkpoint_np` reads back; `compressed`: deflated
+  members (the save evaluator's files; checkpoints stay uncompressed)."""
   names_and_vals, _ = tree_flatten_with_names(tree)
-  np.savez(fname, **{n: _to_numpy(v) for n, v in names_and_vals})
+  (np.savez_compressed if compressed else np.savez)(fname, **{n: _to_numpy(v) for n, v in names_and_vals})
 
 
 def save_train_state(fname, train_state):
